@@ -6,13 +6,19 @@ stage-0 strong-alignment loss mix (L1 + LPIPS + multiscale + adaptive VF + KL +
 StyleGAN-T D), batch 32 per GPU. One "step" = one full training iteration of
 training/training_loop.py (D phase + G phase + gradient sync + Adam + G_ema).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (value = images/sec over all ranks, max-over-rank
-step time). Extra keys: `roofline` (dominant HIP kernel, HIP-event timed during
-the timed region) and `cpu_baseline` (the pure-torch CPU restatement of the same
-iteration on the host cores, bounded sample).
+step time; `ms_per_step` = one timed step). A plain run does only what that figure
+needs: set-up, warm-up, the K timed steps, the line. `--full` adds the measurements
+that take runs of their own and fills their keys (null in a plain run): `roofline`
+(dominant HIP kernel, ranked in untimed pre-pass steps and HIP-event timed during
+the timed region), `step_mfma` (the timed steps priced from the FLOP table) and
+`cpu_baseline` (the pure-torch CPU restatement of the same iteration on the host
+cores, bounded sample). `--dump-outputs DIR` writes what the last timed step left
+its caller (the stepped parameters of G, D and G_ema, that step's loss statistics)
+as DIR/<name>.npy; the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import gc
@@ -47,11 +53,18 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--config", default=CONFIG)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernel timer (untimed pre-pass "
+                         "steps + the dominant region timed in the timed steps: `roofline`), `step_mfma` and the "
+                         "`cpu_baseline` leg. Off by default: those keys are null in a plain run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB in all: a fixed seeded sample of the larger arrays) and DIR/manifest.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-gc-freeze", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true",
-                    help="A/B: no per-launch HIP events in the timed region (no roofline object)")
+                    help="with --full, A/B: no per-launch HIP events in the timed region (no roofline object)")
     ap.add_argument("--timer-steps", type=int, default=1,
                     help="kernel timing in every n-th timed step only (1 = all timed steps, the default). The timed "
                          "steps draw different equivariance outcomes (decode scales), so a region's launches differ in "
@@ -180,6 +193,76 @@ def cpu_baseline(cfg_path, threads):
     return cpu_step.time_iteration(cfg_path, batch=1, threads=threads)
 
 
+DUMP_MAX_ELEMS = 4 * 2**20     # per array: three parameter arrays of 16 MiB (float32) + the loss table < 64 MB
+DUMP_SEED = 20251
+
+
+def _stats_divert():
+    """Set the loss statistics' accumulators (torch_utils/training_stats.py) aside, so that the next step's
+    reports open fresh ones: host-only, no launch and no synchronisation inside the timed loop. Returns what to
+    hand to _stats_restore."""
+    from torch_utils import training_stats
+    earlier, training_stats._registry.live = training_stats._registry.live, {}
+    return earlier
+
+
+def _stats_restore(earlier):
+    """{name: [count, sum, sum_sq] on the CPU, float64} of what was reported since _stats_divert; the earlier
+    accumulators come back with that added, as if nothing had been set aside."""
+    from torch_utils import training_stats
+    last, fresh = {}, training_stats._registry.live
+    for name, slots in fresh.items():
+        for dev, acc in slots.items():
+            row = acc.detach().double().cpu()
+            last[name] = last[name] + row if name in last else row
+            cur = earlier.setdefault(name, {}).get(dev)
+            if cur is None:
+                earlier[name][dev] = acc
+            else:
+                cur += acc
+    training_stats._registry.live = earlier
+    return last
+
+
+def _flat_sample(tensors):
+    """The tensors flattened into one float32 vector; above DUMP_MAX_ELEMS elements a fixed, seeded sample
+    of it: one element from each of DUMP_MAX_ELEMS equal strata (distinct, increasing indices; the offset within
+    a stratum from a generator of its own)."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        lo = np.arange(DUMP_MAX_ELEMS, dtype=np.int64) * n // DUMP_MAX_ELEMS
+        hi = (np.arange(DUMP_MAX_ELEMS, dtype=np.int64) + 1) * n // DUMP_MAX_ELEMS
+        idx = lo + (np.random.default_rng(DUMP_SEED).random(DUMP_MAX_ELEMS) * (hi - lo)).astype(np.int64)
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy(), n
+
+
+def dump_outputs(out_dir, step, stats0, args):
+    """What the last timed step left its caller: TrainingIteration returns nothing, its results are the stepped
+    parameters of G and D (the trainable ones: frozen towers are inputs), the G_ema tensors it averages, and
+    the loss statistics it reported. <name>.npy each; manifest.json names the tensors' element counts."""
+    os.makedirs(out_dir, exist_ok=True)
+    man = {"steps": args.steps, "warmup": args.warmup, "batch": args.batch, "full": args.full, "arrays": {}}
+    groups = {}
+    for phase in step.phases:
+        flags = next(iter(phase.freeze_cache.values()))
+        groups[f"{phase.name}_params"] = [p for p, f in flags if f]
+    groups["G_ema_params"] = list(step._current_ema_pairs()[1])
+    for name, tensors in groups.items():
+        arr, n = _flat_sample(tensors)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        man["arrays"][name] = {"tensors": len(tensors), "elements": n, "saved": int(arr.size), "dtype": str(arr.dtype),
+                               "sample": None if arr.size == n else f"one index from each of `saved` equal strata of the `elements`, default_rng({DUMP_SEED})"}
+    last = _stats_restore(stats0) if stats0 is not None else {}
+    names = sorted(last)
+    table = np.stack([last[k].numpy() for k in names]) if names else np.zeros([0, 3])
+    np.save(os.path.join(out_dir, "loss_stats.npy"), table.astype(np.float64))
+    man["arrays"]["loss_stats"] = {"rows": names, "columns": ["count", "sum", "sum_sq"], "dtype": "float64"}
+    json.dump(man, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1)
+    return {"dir": out_dir, "arrays": sorted(man["arrays"])}
+
+
 def main(argv=None):
     args = parse_args(argv)
     from torch_utils import distributed as dist
@@ -259,7 +342,8 @@ def main(argv=None):
         step.trace = None
     prepass, target = None, None
     n_pre = args.steps if args.timer_prepass < 0 else args.timer_prepass
-    if on_gpu and not args.no_kernel_timer and n_pre > 0:
+    timer_on = args.full and on_gpu and not args.no_kernel_timer
+    if timer_on and n_pre > 0:
         # rank the kernel regions over untimed steps; the timed steps below time only the dominant one. The
         # pre-pass draws the timed steps' seeded outcome sequence (same shapes, same stratified sampling)
         t1 = time.perf_counter()
@@ -305,12 +389,16 @@ def main(argv=None):
     eqt.forward = lambda *a, **k: draws.append(eq_fwd(*a, **k)) or draws[-1]
     venc = step.G.vfm_encoder
     every = max(1, args.timer_every)
-    kernel_timer.enable(on_gpu and not args.no_kernel_timer, every)
-    calib_us = kernel_timer.calibrate() * 1e3 if (on_gpu and not args.no_kernel_timer) else None
+    kernel_timer.enable(timer_on, every)
+    calib_us = kernel_timer.calibrate() * 1e3 if timer_on else None
     kernel_timer.set_target(target)
+    dump = args.dump_outputs is not None and rank == 0
+    stats0 = None
     t0 = time.perf_counter()
     tsteps = max(1, args.timer_steps)
     for i in range(args.steps):
+        if dump and i == args.steps - 1:
+            stats0 = _stats_divert()        # host-only: the last step's statistics land in accumulators of their own
         h0 = getattr(venc, "reuse_hits", 0)
         kernel_timer.new_step(i % tsteps == 0)
         one(args.warmup + i, cur)
@@ -343,8 +431,9 @@ def main(argv=None):
     traffic_table = None
     if os.path.exists(PMC_TRAFFIC):       # committed PMC passes of this workload (tools_dev/pmc_traffic.py)
         traffic_table = json.load(open(PMC_TRAFFIC)).get("kernels")
+    dumped = dump_outputs(args.dump_outputs, step, stats0, args) if dump else None
     roof = kernel_timer.dominant_roofline(HBM_PEAK_GBS, BF16_PEAK_TFLOPS, traffic_table, prepass=prepass) \
-        if on_gpu else None
+        if timer_on else None
     if roof is not None:
         roof["traffic_source"] = os.path.relpath(PMC_TRAFFIC, ROOT) if roof.get("traffic") else None
         n_t = len(range(0, args.steps, tsteps))
@@ -358,9 +447,9 @@ def main(argv=None):
                                      f"runner_up and all_kernels come from {n_pre} untimed pre-pass steps drawing the "
                                      f"timed steps' seeded outcome sequence (every region, the same stratified 1/{every}) "
                                      f"with totals scaled to {args.steps} steps" if prepass is not None else ""))
-    step_mfma = step_flops(draws, hits, args.batch, args.steps, value) if args.config == CONFIG else None
+    step_mfma = step_flops(draws, hits, args.batch, args.steps, value) if (args.full and args.config == CONFIG) else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             _log(rank, "cpu baseline ...")
             cpu = cpu_baseline(args.config, args.cpu_threads)
@@ -387,6 +476,7 @@ def main(argv=None):
             "roofline": roof,
             "step_mfma": step_mfma,
             "cpu_baseline": cpu,
+            "full": args.full, "outputs": dumped,
             # A/B switches set for this run (empty: every default, the tested product path)
             "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("VFM_")},
         }

@@ -3,7 +3,7 @@
 Runs the same TrainingIteration (D phase + G phase + sync + Adam + EMA) on the
 host with every op in its pure-torch form (the `impl='ref'` formulations that
 tests/test_networks_parity.py pins to the reference's golden vectors). Used only
-as bench.py's `cpu_baseline` leg ("port": this package's CPU restatement of the
+as the `cpu_baseline` leg of `bench.py --full` ("port": this package's CPU restatement of the
 reference algorithm; the reference itself cannot travel to the GPU box).
 """
 import copy

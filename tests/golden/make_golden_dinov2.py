@@ -71,5 +71,6 @@ with torch.no_grad():
         put(f"{name}/pooled", pooled[0])
         meta["cases"].append(name)
         print(name, [tuple(f.shape) for f in feats], flush=True)
-np.savez_compressed(OUT, meta=json.dumps(meta), **arrays)
-print("wrote", OUT, os.path.getsize(OUT), "bytes")
+import golden_io  # noqa: E402  (tests/golden_io.py: archives over 1 MiB are written as <stem>.partNN.npz)
+PARTS = golden_io.save_parts(OUT, dict(arrays, meta=np.array(json.dumps(meta))))
+print("wrote", OUT, sum(os.path.getsize(p) for p in PARTS), "bytes")

@@ -112,6 +112,7 @@ for i, (n, step) in enumerate(fc.FULL_GRADS):
     meta["full_grads"].append([n, step])
 meta["g_kwargs"] = {k: v for k, v in g_kwargs.items() if k != "vfm_name"}
 arrays["meta"] = np.array(json.dumps(meta))
-np.savez_compressed(OUT, **arrays)
+import golden_io  # noqa: E402  (tests/golden_io.py: archives over 1 MiB are written as <stem>.partNN.npz)
+PARTS = golden_io.save_parts(OUT, arrays)
 print(f"wrote {OUT}: {len(names)} parameter gradients, loss {meta['loss']:.6e}, group norms {meta['group_norms']}, "
-      f"{os.path.getsize(OUT) / 1024:.1f} KiB")
+      f"{sum(os.path.getsize(p) for p in PARTS) / 1024:.1f} KiB")

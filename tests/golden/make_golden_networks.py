@@ -159,5 +159,6 @@ grad_stats("T/G", G2)
 meta["T/prev_loss_dict"] = loss_obj.prev_loss_dict
 
 arrays["meta"] = np.array(json.dumps(meta))
-np.savez_compressed(OUT, **arrays)
-print(f"wrote {OUT}: {len(arrays)} arrays, {os.path.getsize(OUT) / 1024:.1f} KiB")
+import golden_io  # noqa: E402  (tests/golden_io.py: archives over 1 MiB are written as <stem>.partNN.npz)
+PARTS = golden_io.save_parts(OUT, arrays)
+print(f"wrote {OUT}: {len(arrays)} arrays, {sum(os.path.getsize(p) for p in PARTS) / 1024:.1f} KiB")

@@ -150,5 +150,7 @@ for i, case in enumerate(cr_cases):
     meta["conv2d_resample"].append(dict(kw=case["kw"]))
 
 arrays["meta"] = np.array(json.dumps(meta))
-np.savez_compressed(OUT, **arrays)
-print(f"wrote {OUT}: {len(arrays)} arrays, {os.path.getsize(OUT) / 1024:.1f} KiB")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # tests/
+import golden_io  # noqa: E402  (tests/golden_io.py: archives over 1 MiB are written as <stem>.partNN.npz)
+PARTS = golden_io.save_parts(OUT, arrays)
+print(f"wrote {OUT}: {len(arrays)} arrays, {sum(os.path.getsize(p) for p in PARTS) / 1024:.1f} KiB")

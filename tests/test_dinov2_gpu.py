@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import dinov2_case as dc
+import golden_io
 from det_init import det_init
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "dinov2_golden.npz")
@@ -24,7 +25,7 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "dinov2_golden.npz")
 
 @pytest.fixture(scope="module")
 def golden():
-    z = np.load(GOLDEN)
+    z = golden_io.load_npz(GOLDEN)
     return z, json.loads(str(z["meta"]))
 
 

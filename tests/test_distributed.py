@@ -26,18 +26,36 @@ def _spawn(fn, world=2, *args):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_entry, args=(fn, r, world, port, q, args)) for r in range(world)]
-    for p in procs:
-        p.start()
+    # The ranks are CPU processes (gloo, CPU tensors) on any machine: they start with every GPU hidden. With a
+    # device visible, dist.init() binds rank r to cuda:r, which a machine with fewer GPUs than ranks does not
+    # have: that rank raises while the others wait in the rendezvous until q.get() below times out.
+    hide = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+    saved = {k: os.environ.get(k) for k in hide}
+    os.environ.update(hide)
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     res = {}
-    for _ in procs:
-        r, out = q.get(timeout=300)
-        res[r] = out
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0, p.exitcode
-    for r, out in res.items():
-        if isinstance(out, str) and out.startswith("ERROR"):
-            raise AssertionError(out)
+    try:
+        for _ in procs:
+            r, out = q.get(timeout=300)
+            res[r] = out
+            if isinstance(out, str) and out.startswith("ERROR"):
+                raise AssertionError(out)      # at once: the other ranks may be waiting for this one
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0, p.exitcode
+    finally:
+        for p in procs:                        # no rank outlives a failed test
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
     return res
 
 
@@ -309,10 +327,8 @@ def _bench_worker(rank, world, cfg_path):
     return {"lines": [json.loads(ln) for ln in lines]}
 
 
-def test_bench_main_two_ranks_gloo(tmp_path):
-    """The driver's N > 1 launch of bench.py (one process per device, WORLD_SIZE 2) on a tiny 64-px
-    stage-0 config: both ranks run the same iteration; only rank 0 prints, value = images of all ranks
-    / the max-over-ranks time, parallelism dp2."""
+def _tiny_bench_config(tmp_path):
+    """A tiny 64-px stage-0 config file for bench.main on the CPU."""
     import json
     import yaml
     import net_cases
@@ -334,12 +350,81 @@ def test_bench_main_two_ranks_gloo(tmp_path):
                ema_kimg=10.0, ema_rampup=None, cudnn_benchmark=False)
     path = tmp_path / "tiny.yaml"
     path.write_text(yaml.safe_dump(cfg))
+    return path
+
+
+def test_bench_main_two_ranks_gloo(tmp_path):
+    """The driver's N > 1 launch of bench.py (one process per device, WORLD_SIZE 2) on a tiny 64-px
+    stage-0 config: both ranks run the same iteration; only rank 0 prints, value = images of all ranks
+    / the max-over-ranks time, parallelism dp2."""
+    path = _tiny_bench_config(tmp_path)
     res = _spawn("_bench_worker", 2, str(path))
     assert res[1]["lines"] == []
     (line,) = res[0]["lines"]
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2" and line["steps"] == 2
     assert line["config"]["global_batch"] == 2 and line["value"] > 0
     assert abs(line["value"] - 2 * 2 / (line["ms_per_step"] * 2 / 1e3)) / line["value"] < 1e-2
+
+
+def _bench_dump_worker(rank, world, cfg_path, out_a, out_b):
+    """Two single-process runs of bench.main with --dump-outputs: a plain one, then the same arguments with
+    --full (on the CPU that adds the cpu_baseline leg, after the steps; the kernel timer needs a GPU)."""
+    import contextlib
+    import io
+    import json
+    import functools
+    import bench
+    from oracle import cpu_step
+    torch.set_num_threads(1)        # one fixed order of every reduction: equal inputs then give equal outputs
+    # the leg's own code on a sample of one iteration (its default of 2 + 5 takes over a minute here)
+    cpu_step.time_iteration = functools.partial(cpu_step.time_iteration, iters=1, warmup=0)
+    lines = []
+    for out, extra in ((out_a, []), (out_b, ["--full", "--cpu-threads", "1"])):
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main(["--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "1", "--config", cfg_path,
+                        "--device", "cpu", "--no-gc-freeze", "--dump-outputs", out] + extra)
+        lines += [json.loads(ln) for ln in buf.getvalue().splitlines() if ln.startswith("{")]
+    return {"lines": lines}
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain bench.main run (no --full): --steps sets the timed steps, ms_per_step is the time of one of them,
+    the keys of the --full measurements are null; with --full the cpu_baseline leg fills its key again.
+    --dump-outputs writes the last timed step's results (stepped G / D / G_ema parameters, that step's loss
+    statistics) as float32 / float64 .npy under 64 MB; both runs start from identical inputs and --full changes
+    nothing in the steps, so on one CPU thread their outputs are equal."""
+    import json
+    import numpy as np
+    path = _tiny_bench_config(tmp_path)
+    a, b = tmp_path / "out_a", tmp_path / "out_b"
+    res = _spawn("_bench_dump_worker", 1, str(path), str(a), str(b))
+    plain, full = res[0]["lines"]
+    for line in (plain, full):
+        assert line["steps"] == 2 and line["warmup"] == 0
+        assert line["ms_per_step"] > 0
+        assert abs(line["value"] - 1 / (line["ms_per_step"] / 1e3)) / line["value"] < 1e-2
+        assert line["roofline"] is None and line["step_mfma"] is None      # GPU / flagship-config measurements
+    assert plain["full"] is False and plain["cpu_baseline"] is None
+    assert full["full"] is True and full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["cores"] == 1
+    names = sorted(f.name for f in a.iterdir() if f.suffix == ".npy")
+    assert names == ["D_params.npy", "G_ema_params.npy", "G_params.npy", "loss_stats.npy"]
+    assert names == sorted(f.name for f in b.iterdir() if f.suffix == ".npy")
+    assert sum(f.stat().st_size for f in a.iterdir()) < 64 * 2**20
+    man = json.load(open(a / "manifest.json"))
+    for n in names:
+        xa, xb = np.load(a / n), np.load(b / n)
+        assert xa.dtype in (np.float32, np.float64) and xa.size > 0 and np.isfinite(xa).all(), n
+        assert np.array_equal(xa, xb), n
+    stats = np.load(a / "loss_stats.npy")
+    rows = man["arrays"]["loss_stats"]["rows"]
+    assert stats.shape == (len(rows), 3) and "Loss/G/l1_pixel_loss" in rows
+    # the last step's share alone, not the sum over the shape warm-up and both timed steps: one microbatch, so
+    # each phase reports its skip flag once and the G phase its scalar L1 loss once
+    for name in ("Loss/D/skipped", "Loss/G/skipped", "Loss/G/l1_pixel_loss"):
+        assert stats[rows.index(name), 0] == 1, name
+    for n in ("G_params", "D_params", "G_ema_params"):
+        assert man["arrays"][n]["saved"] == np.load(a / (n + ".npy")).size <= man["arrays"][n]["elements"]
 
 
 def _safety_worker(rank, world):

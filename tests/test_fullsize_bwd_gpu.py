@@ -32,6 +32,7 @@ import pytest
 import torch
 
 import fullsize_case as fc
+import golden_io
 from det_init import det_init
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "fullsize_bwd_golden.
 
 @pytest.fixture(scope="module")
 def golden():
-    z = np.load(GOLDEN)
+    z = golden_io.load_npz(GOLDEN)
     return z, json.loads(str(z["meta"]))
 
 

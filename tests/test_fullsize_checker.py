@@ -9,12 +9,13 @@ import numpy as np
 import torch
 
 import fullsize_case as fc
+import golden_io
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "fullsize_bwd_golden.npz")
 
 
 def _case(name_part):
-    z = np.load(GOLDEN)
+    z = golden_io.load_npz(GOLDEN)
     meta = json.loads(str(z["meta"]))
     i = next(i for i, (n, step) in enumerate(meta["full_grads"]) if name_part in n and step == 1)
     n = meta["full_grads"][i][0]

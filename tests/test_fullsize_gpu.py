@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import fullsize_case as fc
+import golden_io
 from det_init import det_init
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ GOLDEN = __import__("os").path.join(__import__("os").path.dirname(__file__), "go
 
 @pytest.fixture(scope="module")
 def golden():
-    z = np.load(GOLDEN)
+    z = golden_io.load_npz(GOLDEN)
     return z, json.loads(str(z["meta"]))
 
 

@@ -1,4 +1,4 @@
-"""Per-kernel ms/step difference of two bench.py JSON lines (the roofline object's all_kernels table):
+"""Per-kernel ms/step difference of two `bench.py --full` JSON lines (the roofline object's all_kernels table):
 python tools_dev/bench_diff.py A.log B.log [N]"""
 import json
 import sys

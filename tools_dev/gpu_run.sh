@@ -11,10 +11,10 @@ for s in "$@"; do
   case $s in
     tests)   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $out/tests.log 2>&1 ;;
     testsk)  timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread > $out/tests.log 2>&1 ;;
-    bench)   timeout -k 10 900 python bench.py > $out/bench.log 2>&1 ;;
-    benchshape) VFM_TIMER_SHAPES=1 timeout -k 10 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $out/benchshape.log 2>&1 ;;
+    bench)   timeout -k 10 900 python bench.py --full > $out/bench.log 2>&1 ;;
+    benchshape) VFM_TIMER_SHAPES=1 timeout -k 10 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $out/benchshape.log 2>&1 ;;
     benchres) VFM_RESIDUAL_FUSION=0 timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_r0.log 2>&1 && VFM_RESIDUAL_FUSION=1 timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_r1.log 2>&1 && VFM_RESIDUAL_FUSION=0 timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_r2.log 2>&1 && VFM_RESIDUAL_FUSION=1 timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_r3.log 2>&1 ;;
-    benchkt) timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_kt1.log 2>&1 && timeout -k 10 600 python bench.py --no-cpu-baseline --no-kernel-timer > $out/bench_kt0.log 2>&1 && timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_kt3.log 2>&1 && timeout -k 10 600 python bench.py --no-cpu-baseline --no-kernel-timer > $out/bench_kt2.log 2>&1 ;;
+    benchkt) timeout -k 10 600 python bench.py --full --no-cpu-baseline > $out/bench_kt1.log 2>&1 && timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-kernel-timer > $out/bench_kt0.log 2>&1 && timeout -k 10 600 python bench.py --full --no-cpu-baseline > $out/bench_kt3.log 2>&1 && timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-kernel-timer > $out/bench_kt2.log 2>&1 ;;
     benchq)  timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench.log 2>&1 ;;
     benchref) timeout -k 10 600 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --force-ref-ops > $out/bench_ref.log 2>&1 ;;
     prof)    ps=${PROF_STEPS:-20}
@@ -102,8 +102,8 @@ for s in "$@"; do
     r4tests11) timeout -k 10 900 python -u -m pytest tests/test_decoder_attention_gpu.py tests/test_networks_gpu.py tests/test_fullsize_gpu.py tests/test_fullsize_bwd_gpu.py tests/test_graphed_forward_gpu.py -m gpu --maxfail=10 -v --timeout 240 --timeout-method thread > $out/r4tests11.log 2>&1 ;;
     r4tests12) timeout -k 10 900 python -u -m pytest tests/test_specnorm_gpu.py tests/test_patchgan_gpu.py tests/test_networks_gpu.py tests/test_decoder_gpu.py tests/test_attention_f32_gpu.py tests/test_decoder_attention_gpu.py tests/test_gemm_gpu.py -m gpu --maxfail=10 -v --timeout 240 --timeout-method thread > $out/r4tests12.log 2>&1 ;;
     r4tests13) timeout -k 10 900 python -u -m pytest tests/test_decoder_gpu.py tests/test_networks_gpu.py tests/test_fullsize_bwd_gpu.py tests/test_fullsize_gpu.py tests/test_configs_gpu.py -m gpu --maxfail=10 -v --timeout 240 --timeout-method thread > $out/r4tests13.log 2>&1 ;;
-    abtimer) bash tools_dev/ab_args.sh $tag/abtimer "" "--no-kernel-timer" ;;
-    abtimer3) bash tools_dev/ab3_args.sh $tag/abtimer3 "--timer-every 16" "--timer-every 256" "--no-kernel-timer" ;;
+    abtimer) bash tools_dev/ab_args.sh $tag/abtimer "--full" "--full --no-kernel-timer" ;;
+    abtimer3) bash tools_dev/ab3_args.sh $tag/abtimer3 "--full --timer-every 16" "--full --timer-every 256" "--full --no-kernel-timer" ;;
     newpaths) VFM_IM2COL_ROWS=1 VFM_SPLIT_PLANAR8=1 timeout -k 10 900 python -u -m pytest tests/test_specnorm_gpu.py tests/test_patchgan_gpu.py tests/test_gemm_gpu.py tests/test_networks_gpu.py tests/test_fullsize_gpu.py -m gpu --maxfail=10 -v --timeout 240 --timeout-method thread > $out/newpaths.log 2>&1 ;;
     abnew) bash tools_dev/ab_env2.sh $tag/abnew ;;
     dkdvtest) VFM_ATTN32_DKDV_OCC=2 timeout -k 10 600 python -u -m pytest tests/test_attention_f32_gpu.py tests/test_decoder_attention_gpu.py -m gpu -v --timeout 120 --timeout-method thread > $out/dkdvtest.log 2>&1 ;;

@@ -1,5 +1,5 @@
 """Compare the bench line's per-kernel averages (roofline.all_kernels + region -> rocprof kernel names) with the
-rocprofv3 kernel-trace stats of the SAME process (bench.py run under `rocprofv3 --kernel-trace --stats`).
+rocprofv3 kernel-trace stats of the SAME process (`bench.py --full` run under `rocprofv3 --kernel-trace --stats`).
 
   python tools_dev/timer_vs_rocprof.py <bench.log> <run_kernel_trace.csv>
 

@@ -27,6 +27,7 @@ from networks.utils.shared import ResidualBlock, FullyConnectedLayer
 from networks.utils.vit_utils import VisionTransformer, make_vit_backbone, forward_vit
 from networks.utils.vfm_utils import VFM2INTERPOLATION
 from training.diffaug import DiffAugment
+from torch_utils.ops import resize_det
 
 # VFM_DHEAD_FOLDED=0: the per-sample batched GEMMs (stride-0 weight) instead of the batch-folded GEMMs
 _FOLDED = os.environ.get("VFM_DHEAD_FOLDED", "1") == "1"
@@ -383,10 +384,11 @@ class ProjectedDiscriminator(nn.Module):
         res = self.dino.img_resolution
         if x.size(-1) > res and np.random.random() < self.p_crop:
             x = _random_crop(x, res)
+        # (resize_det: F.interpolate with a reproducible backward; torch's scatters with atomic adds)
         if x.size(-1) < res:
-            x = F.interpolate(x, res, mode=self.interpolation, align_corners=False)
+            x = resize_det.interpolate(x, res, mode=self.interpolation, align_corners=False)
         elif x.size(-1) > res:
-            x = F.interpolate(x, res, mode=self.interpolation, align_corners=False, antialias=True)
+            x = resize_det.interpolate(x, res, mode=self.interpolation, align_corners=False, antialias=True)
         x = (x - self._norm_mean) / self._norm_std
         feats = self.dino(x)
         from torch_utils.ops import specnorm_group

@@ -30,7 +30,7 @@ from torch.nn.parameter import Parameter
 
 from torch_utils import misc
 from torch_utils import distributed as dist
-from torch_utils.ops import upfirdn2d, conv2d_resample, bias_act, fma, style_group
+from torch_utils.ops import upfirdn2d, conv2d_resample, bias_act, fma, style_group, resize_det
 from networks.utils.shared import FullyConnectedLayer, MLP, GroupNorm32, StyleSplit, ScaleAdaptiveAvgPool2d
 from networks.utils.shared import DepthwiseConv2d, Conv1x1, LeakyReLU
 from networks.utils.ldm_utils import LDMAdapter, EquivarianceTransform
@@ -667,7 +667,7 @@ class Generator(nn.Module):
         z = enc.z
         if not validation and not is_prior:
             if eq_scale != 1.0:
-                z = F.interpolate(z, scale_factor=eq_scale, mode='bilinear', align_corners=False)
+                z = resize_det.interpolate(z, scale_factor=eq_scale, mode='bilinear', align_corners=False)
             if eq_angle != 0:
                 z = torch.rot90(z, k=eq_angle, dims=[-1, -2])
         z = self.ldm_adapter.decode(z)

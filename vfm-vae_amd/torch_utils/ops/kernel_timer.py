@@ -1,6 +1,6 @@
 """Per-launch timing of named kernels inside a timed region.
 
-bench.py enables the timer around its timed steps; every native op wrapper
+`bench.py --full` enables the timer around its timed steps; every native op wrapper
 opens a region around its launch and reports the launch's ALGORITHMIC bytes
 (unique inputs + outputs + weights at the op boundary) and flops.
 
