@@ -361,6 +361,14 @@ int vfm_attention_fwd(const void* q, const void* k, const void* v, void* o, int 
  * when mask is given (bias / mask may be null). */
 int vfm_conv3x3_nhwc_f32(const float* x, const void* w_pieces, int precision, int ldw, const float* bias,
                          const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int relu, void* stream);
+/* The same convolution with the kernel form chosen by the caller (A/B runs and tests): form 0 = auto (what
+ * vfm_conv3x3_nhwc_f32 runs), 1 = the tiled kernel (a K-tile staged per tap), 2 = the patch-staged kernel
+ * (f32x6 only: a 16 x 16 pixel patch of one image per workgroup, each 32-channel chunk staged once with its
+ * halo for the nine taps; Cin >= 32, Cout % 64 == 0, H % 16 == 0 and W % 16 == 0, else VFM_NO_KERNEL).
+ * Forms 1 and 2 give bit-identical outputs. */
+int vfm_conv3x3_nhwc_f32_form(const float* x, const void* w_pieces, int precision, int ldw, const float* bias,
+                              const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int relu,
+                              void* stream, int form);
 /* Input gradient of a 3x3 / pad 1 conv with few input channels (the VGG16 image layer, C = 3), exact fp32
  * FMAs on the VALU (replaces torch.nn.grad.conv2d_input = MIOpen fp32 Winograd there):
  *   dx[b, c, y, x] = sum_{o, ky, kx} w[o, c, ky, kx] dz[b, y + 1 - ky, x + 1 - kx, o].

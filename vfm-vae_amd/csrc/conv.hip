@@ -26,6 +26,8 @@
 // implicit: each thread owns 4 pixel rows and one 4-channel column of the tile; a k-tile (32
 // channels of one tap, or for Cin < 32 several taps) becomes one 16-B load per row at
 // (p + dy*W + dx)*Cin + c, zero outside the image. The 9 shifted reads of a pixel hit L2.
+// For the f32x6 products at Cin >= 32 on planes that are multiples of 16 x 16 the patch-staged form
+// below (conv3x3_patch_kernel) stages each 32-channel chunk once for its nine taps; bit-identical.
 #include "vfm_common.h"
 
 #include <cstdlib>
@@ -51,6 +53,7 @@ struct ConvArgs {
     int M, H, W, Cin, lc, Cout, K;
     FastDiv fW, fH;
     int relu;
+    int pw, ph;                 // patch form: patches per image row / column (fW, fH then divide by these)
 };
 
 // [rows][32 k] bf16 image, 64-B rows: 16-B chunk ch of row at chunk ch ^ ((row >> 2) & 3) -- the 16
@@ -311,11 +314,211 @@ int launch(const ConvArgs& a, hipStream_t st) {
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Patch-staged form of the f32x6 conv (Cin >= 32, H and W multiples of PT). The nine taps of a
+// 32-channel chunk read the same activations shifted by one pixel, so a workgroup takes a PT x PT
+// pixel patch of ONE image (256 GEMM rows) and per chunk stages the patch with its one-pixel halo
+// ONCE -- (PT + 2)^2 pixels x 32 channels: fp32 loads, zero outside the image, split_pieces<3>, three
+// piece images -- and runs the nine taps from it: the A fragment of tap (ty, tx) is the ds_read_b128
+// at the lane's pixel + (ty, tx). Loads, splits and A stores per output pixel drop from 9 to
+// (PT + 2)^2 / PT^2 = 1.27 per chunk; fragment reads and MFMAs are those of the tiled kernel. The B
+// tile of each tap (pre-split weights) is double-buffered through registers as there. The next
+// chunk's patch is loaded into registers at the start of a chunk (in flight under its nine taps)
+// and split + stored at the chunk boundary between two barriers: one exposed staging phase per
+// nine K-tiles. K order (chunk-major, tap-minor), the k -> MFMA slot mapping, the Terms<3> order
+// and the two accumulators are the tiled kernel's, so the outputs are bit-identical to it.
+//
+// Patch image: pixel (y, x) of the halo patch is image row y * PPITCH + x, 64-B rows swizzled as
+// k32_off over x. PPITCH = 20 makes a patch row a whole number of 256-B bank rows, so the bank slot
+// of a 16-B chunk is 4 (x & 3) + (ch ^ ((x >> 2) & 3)); a 32-row MFMA block is two patch rows of 16
+// pixels, and each ds_read_b128 lane group (8 pixels x0 + tx + {0-3, 12-15} of one row, 8 pixels
+// x0 + tx + {4-11} of the other) covers the 16 slots once for every tap shift tx
+// (tools_dev/conv_patch_banks.py enumerates them).
+constexpr int PT = 16;
+constexpr int PHALO = PT + 2;
+constexpr int PPITCH = 20;
+constexpr int PROW = PPITCH * ROWB;             // bytes of one patch row of a piece image
+constexpr int PIMG = PHALO * PROW;              // bytes of one piece image of the patch
+
+// thread -> (halo pixel e = tid / 8 + 64 u, 4-channel column tid % 8) of the [PHALO^2][32] fp32 patch
+struct StagePatch {
+    static constexpr int PER = (PHALO * PHALO + 63) / 64;
+    uint4 r[PER];
+    int goff[PER];    // element offset of the thread's 4 channels in chunk 0, -1 outside the image
+    int loff[PER];    // byte offset in a piece image, -1 past the patch
+    __device__ __forceinline__ void init(const ConvArgs& a, int b, int y0, int x0, int tid) {
+        const int c4 = tid & 7;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int e = tid / 8 + 64 * u;
+            const int ey = e / PHALO, ex = e - PHALO * ey;
+            const int gy = y0 - 1 + ey, gx = x0 - 1 + ex;
+            const bool in = e < PHALO * PHALO;
+            const bool ok = in && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            goff[u] = ok ? ((b * a.H + gy) * a.W + gx) * a.Cin + 4 * c4 : -1;
+            loff[u] = in ? ey * PROW + k32_off(ex, c4 >> 1) + 8 * (c4 & 1) : -1;
+        }
+    }
+    __device__ __forceinline__ void load(const ConvArgs& a, int cc) {
+#pragma unroll
+        for (int u = 0; u < PER; ++u)
+            r[u] = goff[u] >= 0
+                       ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (unsigned)(goff[u] + 32 * cc) * 4u)
+                       : make_uint4(0, 0, 0, 0);
+    }
+    __device__ __forceinline__ void store(unsigned char* img) const {
+#pragma unroll
+        for (int u = 0; u < PER; ++u)
+            if (loff[u] >= 0) put4<3>(img, PIMG, loff[u], r[u]);
+    }
+};
+
+// PT x PT pixels x BN couts, 512 threads: waves as 4 (M: 4 patch rows each) x 2 (N), each 64 rows x BN / 2 columns.
+template <int BN>
+__global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(ConvArgs a) {
+    constexpr int NP = 3, THREADS = 512;
+    constexpr int NJ = BN / 64;
+    constexpr int IMG_B = BN * ROWB;
+    constexpr int STAGE_B = NP * IMG_B;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    unsigned char* pa = lds;                    // NP piece images of the patch
+    unsigned char* pb = lds + NP * PIMG;        // two B stages of NP piece images
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 3, wn = wave >> 2;
+    const int tiles_n = a.Cout / BN;
+    // XCD-aware remap as in conv3x3_kernel: one XCD takes consecutive tiles, i.e. all Cout tiles of a
+    // patch and then its row neighbours, which share halo columns
+    const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int patch = tile / tiles_n, n0 = (tile - patch * tiles_n) * BN;
+    const int q = (int)fdiv((uint32_t)patch, a.fW);         // fW, fH: divisors pw, ph
+    const int b = (int)fdiv((uint32_t)q, a.fH);
+    const int x0 = (patch - q * a.pw) * PT, y0 = (q - b * a.ph) * PT;
+
+    StagePatch sp;
+    StageB<BN, NP, THREADS> sb;
+    sp.init(a, b, y0, x0, tid);
+    f32x16 acc[2][NJ], accs[2][NJ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = accs[i][j] = f32x16{};
+
+    // row r of the wave's 32-row block i is patch pixel (4 wm + 2 i + (r >> 4), r & 15)
+    const int r = lane & 31, hh = lane >> 5;
+    const int fy = 4 * wm + (r >> 4), fx = r & 15;
+
+    const int NC = a.Cin >> 5, KT = 9 * NC;
+    sp.load(a, 0);
+    sb.load(a, n0, 0, tid);
+    sp.store(pa);
+    sb.store(pb, tid);
+    sb.load(a, n0, BK, tid);
+    if (NC > 1) sp.load(a, 1);
+    lds_barrier();
+    int cc = 0, tap = 0;
+    for (int kt = 0; kt < KT; ++kt) {
+        const int ty = tap / 3, tx = tap - 3 * ty;
+        const int x = fx + tx;
+        const int ao = (fy + ty) * PROW + x * ROWB + 16 * (hh ^ ((x >> 2) & 3));
+        const unsigned char* cb = pb + (kt & 1) * STAGE_B;
+#pragma unroll
+        for (int s = 0; s < BK / 16; ++s) {
+            bf16x8 af[NP][2], bf[NP][NJ];
+            const unsigned char* ca = pa + (ao ^ (32 * s));         // chunk (2 s + hh) ^ swizzle
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) af[p][i] = *reinterpret_cast<const bf16x8*>(ca + p * PIMG + 2 * i * PROW);
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) bf[p][j] = frag(cb + p * IMG_B, NJ * wn + j, s, lane);
+            }
+#pragma unroll
+            for (int t = 0; t < Terms<NP>::N; ++t)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) {
+                        f32x16& c = (t == Terms<NP>::N - 1) ? acc[i][j] : accs[i][j];
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[Terms<NP>::a(t)][i], bf[Terms<NP>::b(t)][j], c,
+                                                                    0, 0, 0);
+                    }
+            // between the two MFMA steps: the B tile of K-tile kt+1 into the other stage, then the loads of kt+2
+            if (s == 0 && kt + 1 < KT) {
+                sb.store(pb + ((kt + 1) & 1) * STAGE_B, tid);
+                if (kt + 2 < KT) sb.load(a, n0, (kt + 2) * BK, tid);
+            }
+        }
+        if (++tap == 9) {
+            tap = 0;
+            ++cc;
+            if (cc < NC) {
+                // chunk boundary: every wave is done with the patch, then the next chunk (in registers
+                // since the start of this one) is split and stored, and the chunk after it requested
+                lds_barrier();
+                sp.store(pa);
+                if (cc + 1 < NC) sp.load(a, cc + 1);
+            }
+        }
+        lds_barrier();
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] += accs[i][j];
+
+    // acc[i][j][e] = out[pixel (y0 + 4wm + 2i + (row >> 4), x0 + (row & 15))][n], row = (e&3) + 8(e>>2) + 4hh
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int n = n0 + 32 * (NJ * wn + j) + r;
+        const float bn = a.bias ? a.bias[n] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = (e & 3) + 8 * (e >> 2) + 4 * hh;
+                const int m = (b * a.H + y0 + 4 * wm + 2 * i + (row >> 4)) * a.W + x0 + (row & 15);
+                const unsigned o = (unsigned)(m * a.Cout + n) * 4u;     // byte offset (host: M * Cout < 2^30)
+                float v = acc[i][j][e] + bn;
+                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.mask && !(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.mask) + o) > 0.f)) v = 0.f;
+                *reinterpret_cast<float*>(reinterpret_cast<char*>(a.out) + o) = v;
+            }
+    }
+}
+
+template <int BN>
+int launch_patch(ConvArgs a, int B, hipStream_t st) {
+    const size_t lds = 3 * PIMG + 2 * 3 * BN * ROWB;
+    static bool attr[MAXDEV] = {};
+    const int dv_attr = cur_dev();
+    if (!attr[dv_attr]) {
+        (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        attr[dv_attr] = true;
+    }
+    a.pw = a.W / PT;
+    a.ph = a.H / PT;
+    a.fW = make_fastdiv((uint32_t)a.pw);
+    a.fH = make_fastdiv((uint32_t)a.ph);
+    const long long tiles = (long long)B * a.pw * a.ph * (a.Cout / BN);
+    if (tiles > 0x7fffffff) return VFM_ERR_ARGS;
+    VFM_LAUNCH((conv3x3_patch_kernel<BN>), dim3((unsigned)tiles), dim3(512), lds, st, a);
+    return launch_status();
+}
+
+// shapes the patch form takes
+inline bool patch_takes(int np, int H, int W, int Cin, int Cout) {
+    return np == 3 && Cin >= 32 && Cout % 64 == 0 && H % PT == 0 && W % PT == 0;
+}
+
 }  // namespace
 
-extern "C" int vfm_conv3x3_nhwc_f32(const float* x, const void* w_pieces, int precision, int ldw, const float* bias,
-                                    const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int relu,
-                                    void* stream) {
+extern "C" int vfm_conv3x3_nhwc_f32_form(const float* x, const void* w_pieces, int precision, int ldw,
+                                         const float* bias, const float* mask, float* out, int B, int H, int W, int Cin,
+                                         int Cout, int relu, void* stream, int form) {
+    if (form < 0 || form > 2) return VFM_ERR_ARGS;
     if (!x || !w_pieces || !out || B <= 0 || H <= 0 || W <= 0 || H > 32767 || W > 32767) return VFM_ERR_ARGS;
     if (precision != VFM_F32 && precision != VFM_F32X3) return VFM_ERR_ARGS;
     const int np = precision == VFM_F32 ? 3 : 2;
@@ -345,11 +548,23 @@ extern "C" int vfm_conv3x3_nhwc_f32(const float* x, const void* w_pieces, int pr
         const char* e = getenv("VFM_CONV_N64");
         return e && e[0] == '2';
     }();
+    // form 2: the patch-staged kernel or VFM_NO_KERNEL; form 0 (auto) takes it for every shape it covers: it
+    // measured 0.70-0.83 of the tiled kernel's time on all 16 layer shapes of the step, the Cout = 64 ones
+    // on its BN = 64 instantiation included (profiles/r7_b_vggbench_patch_ab.txt)
+    const bool patch_ok = patch_takes(np, H, W, Cin, Cout);
+    if (form == 2 && !patch_ok) return VFM_NO_KERNEL;
+    if (form != 1 && patch_ok) return (Cout % 128 == 0) ? launch_patch<128>(a, B, st) : launch_patch<64>(a, B, st);
     if (np == 3) {
         if (Cout % 128 == 0) return launch<256, 128, 3>(a, st);
         return wide64 ? launch<256, 64, 3>(a, st) : launch<128, 64, 3>(a, st);
     }
     return (Cout % 128 == 0) ? launch<128, 128, 2>(a, st) : launch<128, 64, 2>(a, st);
+}
+
+extern "C" int vfm_conv3x3_nhwc_f32(const float* x, const void* w_pieces, int precision, int ldw, const float* bias,
+                                    const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int relu,
+                                    void* stream) {
+    return vfm_conv3x3_nhwc_f32_form(x, w_pieces, precision, ldw, bias, mask, out, B, H, W, Cin, Cout, relu, stream, 0);
 }
 
 // ---------------------------------------------------------------------------------------------

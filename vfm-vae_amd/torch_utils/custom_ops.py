@@ -137,6 +137,8 @@ SIGNATURES = {
     "vfm_maxpool2x2_bwd_nhwc_f32": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
     "vfm_conv3x3_nhwc_f32": [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_vp],
+    "vfm_conv3x3_nhwc_f32_form": [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_vp, c_int],
     "vfm_attention_f32_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_llp, c_llp, c_llp,
                               c_llp, c_float, c_int, c_vp],
     "vfm_gemm9_set_mode": [c_int],

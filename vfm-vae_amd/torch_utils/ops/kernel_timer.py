@@ -387,6 +387,19 @@ def rocprof_name(region):
     return pat.format(T=T, K=K)
 
 
+def rocprof_names(region):
+    """Every rocprof kernel-name pattern a region's launches may carry, the kernel most of them run first:
+    rocprof_name(region), and ahead of it for the f32x6 conv regions the patch-staged conv kernel that their
+    layers with 16-divisible planes run on (csrc/conv.hip; all but the equivariance scales' odd planes)."""
+    roc = rocprof_name(region)
+    if roc is None:
+        return []
+    if roc.startswith("conv3x3_kernel<") and roc.endswith(", 3>"):
+        bn = roc.split(", ")[1]
+        return [f"conv3x3_patch_kernel<{bn}>", roc]
+    return [roc]
+
+
 def _roof(name, r, hbm_peak_gbs, mfma_peak_tflops):
     t = r["total_ms"] / 1e3
     note = None
@@ -437,12 +450,14 @@ def dominant_roofline(hbm_peak_gbs, mfma_peak_tflops, traffic_table=None, steps=
         achieved, peak, unit, note = _roof(name, r, hbm_peak_gbs, mfma_peak_tflops)
         roc = rocprof_name(name)
         traffic = None
-        if traffic_table and roc:
+        for pat in (rocprof_names(name) if traffic_table else []):     # the first of the region's kernels with a row
             hits = [(v["dispatches_fetch_pass"], v["traffic_bytes_per_launch"]) for k, v in traffic_table.items()
-                    if roc_match(roc, k) and v.get("traffic_bytes_per_launch")]
+                    if roc_match(pat, k) and v.get("traffic_bytes_per_launch")]
             n = sum(h[0] for h in hits)
             if n:
                 traffic = int(sum(c * t for c, t in hits) / n)
+                roc = pat
+                break
         bpl = int(r["bytes"] / r["launches"])
         return {"bound": r["bound"], "achieved": round(achieved, 1), "peak": peak, "unit": unit,
                 "frac": round(achieved / peak, 4), "traffic": traffic, "kernel": name, "rocprof_kernel": roc,

@@ -11,6 +11,8 @@ weight gradients.
 `vgg16_taps(x, convs)` returns the five LPIPS taps (relu1_2, relu2_2, relu3_3, relu4_3,
 relu5_3) as NCHW-shaped views of NHWC tensors.
 """
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -18,6 +20,11 @@ from .. import custom_ops
 from . import kernel_timer
 
 _lib = custom_ops.get_native()
+
+# VFM_CONV_PATCH (read once, here): 1 (default) lets the library route the f32x6 layers it measured faster to
+# the patch-staged conv kernel (csrc/conv.hip conv3x3_patch_kernel), 0 keeps every layer on the tiled kernel.
+# The two forms are bit-identical; tests flip this attribute.
+CONV_PATCH = os.environ.get("VFM_CONV_PATCH", "1") != "0"
 
 # torchvision vgg16 cfg D up to relu5_3: conv channels, 'M' pool; taps after these conv indices
 _CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512]
@@ -87,13 +94,14 @@ def conv3x3(x, w, bias=None, relu=False, mask=None):
     out = torch.empty(B, H, W, Cout, dtype=torch.float32, device=x.device)
     flops = 2 * B * H * W * Cout * 9 * Cin
     # one timer region per kernel instantiation (BN = 128 / 64 output channels per tile), as
-    # rocprofv3 names them: conv3x3_kernel<BM, 128, NP> / <128, 64, NP> (kernel_timer.rocprof_name)
+    # rocprofv3 names them: conv3x3_kernel<BM, 128, NP> / <128, 64, NP>, and conv3x3_patch_kernel<128> for the
+    # layers the library routes to the patch-staged form (kernel_timer.rocprof_names)
     with kernel_timer.region(f"conv3x3_nhwc<{tag},{128 if Cout % 128 == 0 else 64}>",
                              4 * (x.numel() + out.numel() + Cout * 9 * Cin), flops, "mfma"):
-        rc = _lib.vfm_conv3x3_nhwc_f32(x.data_ptr(), w.data_ptr(), prec, Kp, custom_ops.ptr(bias),
-                                       custom_ops.ptr(mask), out.data_ptr(), B, H, W, Cin, Cout, int(relu),
-                                       custom_ops.stream_ptr(x.device))
-    custom_ops.check(rc, "vfm_conv3x3_nhwc_f32")
+        rc = _lib.vfm_conv3x3_nhwc_f32_form(x.data_ptr(), w.data_ptr(), prec, Kp, custom_ops.ptr(bias),
+                                            custom_ops.ptr(mask), out.data_ptr(), B, H, W, Cin, Cout, int(relu),
+                                            custom_ops.stream_ptr(x.device), 0 if CONV_PATCH else 1)
+    custom_ops.check(rc, "vfm_conv3x3_nhwc_f32_form")
     return out
 
 
