@@ -16,9 +16,9 @@
  *     legacy default stream). No host synchronisation, no allocation: every entry
  *     point is capturable into a hipGraph.
  *   - Return value: VFM_OK (0) on success, VFM_ERR_ARGS (-2) for an invalid
- *     argument, VFM_NO_KERNEL (-1) when no specialisation exists (only
- *     `vfm_filtered_lrelu`, mirroring `filtered_lrelu.cpp:51-56`), or a positive
- *     hipError_t from the launch.
+ *     argument, VFM_NO_KERNEL (-1) when no specialisation exists
+ *     (`vfm_filtered_lrelu`, mirroring `filtered_lrelu.cpp:51-56`, and the window
+ *     length of `vfm_ssim_*`), or a positive hipError_t from the launch.
  *   - dtype codes: VFM_F32, VFM_F16, VFM_BF16, VFM_F64. Arithmetic is fp32
  *     (fp64 for VFM_F64); filters are always fp32.
  */
@@ -726,6 +726,26 @@ int vfm_posterior_fwd(const float* params, const float* eps, float* z, float* kl
                       void* stream);
 int vfm_posterior_bwd(const float* params, const float* eps, const float* dz, const float* dkl, float* dparams,
                       int B, int C, long long P, void* stream);
+
+/* ---- Gaussian SSIM loss (replaces the torchmetrics StructuralSimilarityIndexMeasure the reference
+ * builds at training/loss.py:150-152 and calls on clamped images at :257-260: two clamps, two reflect
+ * pads, a 121-tap grouped convolution of five stacked planes and ~12 elementwise kernels, and their
+ * backward): preds / target fp32 NCHW contiguous [B, C, H, W], H, W >= ksize; taps: ksize host floats
+ * (the normalised 1-d Gaussian; the window is taps (x) taps), ksize must be 11 (else VFM_NO_KERNEL).
+ * out (0-dim) = mean over planes and the (H-10) x (W-10) valid windows of
+ * (2 mp mt + c1)(2 spt + c2) / ((mp^2 + mt^2 + c1)(spp + stt + c2)); the reflect-padded border the
+ * reference computes and drops never reaches it. clamp != 0: both images are clamped to [lo, hi]
+ * on load (torch.clamp semantics, NaN passes through). partials holds vfm_ssim_fwd_partials floats
+ * (one per block; summed in a fixed order by a second launch: deterministic, no atomics).
+ * bwd: dout (device scalar) -> dpreds [B, C, H, W], recomputed from the two images (nothing saved),
+ * masked by lo <= preds <= hi when clamp != 0. The gradient to target is the same call with preds
+ * and target swapped. */
+int vfm_ssim_fwd_partials(int B, int C, int H, int W);
+int vfm_ssim_fwd(const float* preds, const float* target, float* partials, float* out, const float* taps, int ksize,
+                 float c1, float c2, float lo, float hi, int clamp, int B, int C, int H, int W, void* stream);
+int vfm_ssim_bwd(const float* preds, const float* target, const float* dout, float* dpreds, const float* taps,
+                 int ksize, float c1, float c2, float lo, float hi, int clamp, int B, int C, int H, int W,
+                 void* stream);
 
 /* ---- BatchNormLocal (1-d) + LeakyReLU of the projected discriminator's heads (replaces
  * networks/discriminator.py:45-71 + the head blocks' nn.LeakyReLU(0.2), :102-109): x fp32 [B, C, L] in

@@ -119,6 +119,11 @@ SIGNATURES = {
     "vfm_dwconv2d_fwd_mfma": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "vfm_posterior_fwd": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_vp],
     "vfm_posterior_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_vp],
+    "vfm_ssim_fwd_partials": [c_int, c_int, c_int, c_int],
+    "vfm_ssim_fwd": [c_vp, c_vp, c_vp, c_vp, c_fp, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
+                     c_int, c_int, c_vp],
+    "vfm_ssim_bwd": [c_vp, c_vp, c_vp, c_vp, c_fp, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
+                     c_int, c_int, c_vp],
     "vfm_dwconv2d_bwd_weight_mfma_tiles": [c_int, c_int, c_int, c_int, c_int, c_int],
     "vfm_dwconv2d_bwd_weight_mfma": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "vfm_bnl1d_lrelu_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_vp],

@@ -328,6 +328,7 @@ _ROC = {
     "residual_layer_norm": "ln_rows<", "codebook_argmax": "codebook_argmax_kernel<",
     "convnext_mlp_fwd": "mlp_fwd<", "pw_gemm_gelu_bwd": "pw_gemm_gelu<1, ",
     "attention_fwd": "attn_fwd_d64",
+    "ssim_fwd": "ssim_fwd", "ssim_bwd": "ssim_bwd",
 }
 _NP = {"f32x6": 3, "f32x3": 2, "bf16": 1}
 _TNAME = {"f32": "float", "bf16": "__hip_bfloat16", "f16": "__half", "f64": "double"}

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from torch_utils import training_stats
 from torch_utils import distributed as dist
 from torch_utils.ops import upfirdn2d
+from torch_utils.ops import decoder_ops
 from training.lpips import LPIPS
 from networks.utils.vfm_utils import VFM2INTERPOLATION
 from networks.utils.dataclasses import GeneratorForwardOutput, DiscriminatorForwardOutput
@@ -106,13 +107,23 @@ def _gaussian_window(size, sigma, device, dtype):
 class SSIM(nn.Module):
     """Gaussian SSIM (11x11, sigma 1.5, k1 .01, k2 .03, reflect padding, mean),
     the torchmetrics StructuralSimilarityIndexMeasure defaults used by the
-    reference (loss.py:150) with `data_range`."""
+    reference (loss.py:150) with `data_range`. `clamp=(lo, hi)` clamps both images first (the
+    reference's call site, loss.py:257-260). fp32 ROCm images with the 11-tap window run on the HIP
+    kernels (torch_utils/ops/ssim_hip.py: the clamp fused in, no padding, no convolution); everything
+    else, and `decoder_ops.set_force_ref(True)`, takes the torch formulation below."""
 
     def __init__(self, data_range=2.0, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
         super().__init__()
         self.data_range, self.kernel_size, self.sigma, self.k1, self.k2 = data_range, kernel_size, sigma, k1, k2
 
-    def forward(self, preds, target):
+    def forward(self, preds, target, clamp=None):
+        if preds.is_cuda and preds.dtype == torch.float32 and not decoder_ops.force_ref():
+            from torch_utils.ops import ssim_hip
+            if ssim_hip.supported(preds, target, self.kernel_size):
+                return ssim_hip.ssim(preds, target, self.kernel_size, self.sigma, (self.k1 * self.data_range) ** 2,
+                                     (self.k2 * self.data_range) ** 2, clamp)
+        if clamp is not None:
+            preds, target = preds.clamp(*clamp), target.clamp(*clamp)
         c = preds.shape[1]
         g = _gaussian_window(self.kernel_size, self.sigma, preds.device, preds.dtype)
         win = (g[:, None] * g[None, :])[None, None].repeat(c * 5, 1, 1, 1)
@@ -269,7 +280,7 @@ class TotalLoss:
         return self.perceptual_module(real_img, gen_img).mean()
 
     def calculate_ssim_loss(self, real_img, gen_img):
-        return 1.0 - self.ssim_module(gen_img.clamp(-1, 1), real_img.clamp(-1, 1))
+        return 1.0 - self.ssim_module(gen_img, real_img, clamp=(-1, 1))
 
     def calculate_cur_vf_loss_weight(self, rec_loss, vf_loss, last_layer):
         if not self.use_adaptive_vf_loss:
