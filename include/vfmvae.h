@@ -17,8 +17,9 @@
  *     point is capturable into a hipGraph.
  *   - Return value: VFM_OK (0) on success, VFM_ERR_ARGS (-2) for an invalid
  *     argument, VFM_NO_KERNEL (-1) when no specialisation exists
- *     (`vfm_filtered_lrelu`, mirroring `filtered_lrelu.cpp:51-56`, and the window
- *     length of `vfm_ssim_*`), or a positive hipError_t from the launch.
+ *     (`vfm_filtered_lrelu`, mirroring `filtered_lrelu.cpp:51-56`, the window
+ *     length of `vfm_ssim_*`, k > 64 of `vfm_gram_topk` / `vfm_cknna_terms`), or a
+ *     positive hipError_t from the launch.
  *   - dtype codes: VFM_F32, VFM_F16, VFM_BF16, VFM_F64. Arithmetic is fp32
  *     (fp64 for VFM_F64); filters are always fp32.
  */
@@ -746,6 +747,34 @@ int vfm_ssim_fwd(const float* preds, const float* target, float* partials, float
 int vfm_ssim_bwd(const float* preds, const float* target, const float* dout, float* dpreds, const float* taps,
                  int ksize, float c1, float c2, float lo, float hi, int clamp, int B, int C, int H, int W,
                  void* stream);
+
+/* ---- Alignment analysis: nearest neighbours by inner product and the CKNNA sums (replace
+ * tools/evaluate_alignment/metrics.py:191-238 `AlignmentMetrics.cknna` -- two dense N x N Gram matrices,
+ * torch.topk on clones of them, three pairs of scattered N x N masks -- and :241-260 `hsic_unbiased` on the
+ * masked copies with its N x N . N x N torch.mm, three times; also the Gram + argsort of :283-296
+ * `compute_nearest_neighbors`).
+ * vfm_gram_topk: feats fp32 row-major [N][ld], ld >= D. For every row i the k largest <f_i, f_j> over j
+ *   (j != i when exclude_self): idx int32 [N][k], val fp32 [N][k], descending value, equal values by
+ *   ascending index (-0.0 == 0.0). Products are exact fp32 on the fp32 MFMA, one accumulator per score over
+ *   the whole of D; the result does not depend on `splits`. The score matrix never reaches memory: ws holds
+ *   vfm_gram_topk_ws bytes (splits partial lists per row; 0 bytes and ws may be NULL for one split).
+ *   1 <= k <= N - exclude_self (else VFM_ERR_ARGS), k <= 64 (else VFM_NO_KERNEL), D >= 1, finite features.
+ * vfm_gram_topk_ws: host query; returns the workspace bytes (negative: VFM_ERR_ARGS) and stores the split
+ *   count used for `splits` (0: chosen to fill the chip; never more than the 128-column tiles of N, or 64)
+ *   in *chosen.
+ * vfm_cknna_terms: the two neighbour lists (idxK, valK), (idxL, valL), each [N][k] -> out[9] fp64,
+ *   out[3 h + t] for h = 0: hsic_unbiased(M o K, M o L), 1: (M_K o K, M_K o K), 2: (M_L o L, M_L o L), with
+ *   M(i) the intersection of row i's lists, and t = 0: sum_{(i,j),(j,i) in mask} A_ij B_ji, 1: sum A . sum B,
+ *   2: sum_i sum_{j in mask(i)} A_ij rowsum(B)_j = sum(A @ B). fp64 accumulation in a fixed order, no
+ *   atomics. ws holds vfm_cknna_terms_ws(N) bytes. k <= 64 (else VFM_NO_KERNEL). Precondition: no list holds
+ *   its own row (lists made with exclude_self != 0): hsic_unbiased zeroes the diagonal, and every list entry is
+ *   taken as off-diagonal. */
+long long vfm_gram_topk_ws(int N, int k, int splits, int* chosen);
+int vfm_gram_topk(const float* feats, long long ld, int N, int D, int k, int exclude_self, int splits, int* idx,
+                  float* val, void* ws, void* stream);
+long long vfm_cknna_terms_ws(int N);
+int vfm_cknna_terms(const int* idxK, const float* valK, const int* idxL, const float* valL, int N, int k, double* out,
+                    void* ws, void* stream);
 
 /* ---- BatchNormLocal (1-d) + LeakyReLU of the projected discriminator's heads (replaces
  * networks/discriminator.py:45-71 + the head blocks' nn.LeakyReLU(0.2), :102-109): x fp32 [B, C, L] in

@@ -124,6 +124,10 @@ SIGNATURES = {
                      c_int, c_int, c_vp],
     "vfm_ssim_bwd": [c_vp, c_vp, c_vp, c_vp, c_fp, c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_int,
                      c_int, c_int, c_vp],
+    "vfm_gram_topk_ws": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "vfm_gram_topk": [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "vfm_cknna_terms_ws": [c_int],
+    "vfm_cknna_terms": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
     "vfm_dwconv2d_bwd_weight_mfma_tiles": [c_int, c_int, c_int, c_int, c_int, c_int],
     "vfm_dwconv2d_bwd_weight_mfma": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "vfm_bnl1d_lrelu_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_vp],
@@ -284,6 +288,8 @@ def get_native():
             lib.vfm_channel_rms_norm_rows.restype = c_ll
             lib.vfm_specnorm_workspace_floats.restype = c_ll
             lib.vfm_dwconv2d_fwd_mfma_units.restype = c_ll
+            lib.vfm_gram_topk_ws.restype = c_ll
+            lib.vfm_cknna_terms_ws.restype = c_ll
             _lib = lib
     return _lib
 

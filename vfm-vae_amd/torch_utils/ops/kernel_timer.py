@@ -329,6 +329,7 @@ _ROC = {
     "convnext_mlp_fwd": "mlp_fwd<", "pw_gemm_gelu_bwd": "pw_gemm_gelu<1, ",
     "attention_fwd": "attn_fwd_d64",
     "ssim_fwd": "ssim_fwd", "ssim_bwd": "ssim_bwd",
+    "gram_topk": "gram_topk_kernel", "cknna_terms": "cknna_rows",
 }
 _NP = {"f32x6": 3, "f32x3": 2, "bf16": 1}
 _TNAME = {"f32": "float", "bf16": "__hip_bfloat16", "f16": "__half", "f64": "double"}
