@@ -352,6 +352,38 @@ int vfm_attention_fwd(const void* q, const void* k, const void* v, void* o, int 
                       const long long* sq, const long long* sk, const long long* sv, const long long* so,
                       float scale, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Frozen Qwen2.5-VL vision tower (csrc/qwen.hip; HF Qwen2_5_VisionTransformerPretrainedModel under bf16
+ * autocast, reference networks/utils/vfms/qwen_utils.py:204-261). Forward only.
+ *
+ * Varlen RoPE attention: qkv bf16 [T, 3, H, head_dim] (the packed projection, read in place), cos / sin fp32
+ * [T, head_dim] in the duplicated form (entry d + head_dim/2 equals entry d; the first half is read),
+ * cu_seqlens int32 [S + 1] in device memory (non-decreasing, cu[0] = 0, cu[S] = T), o bf16 [T, H head_dim].
+ * A query attends to the keys of its own segment [cu[s], cu[s+1]) only; q and k are rotated
+ * (x cos + rotate_half(x) sin, fp32) and rounded to bf16 as they are loaded; softmax in fp32, P rounded to
+ * bf16 for P.V. max_seqlen is a host-side hint of the longest segment (<= 0: unknown) that only selects the
+ * workgroup size. head_dim 80 only (else VFM_NO_KERNEL); 16-B aligned bases. */
+int vfm_rope_attention_varlen(const void* qkv, const float* cos, const float* sin, const int* cu_seqlens, void* o,
+                              int T, int H, int head_dim, int S, float scale, int max_seqlen, void* stream);
+
+/* RMSNorm rows on a stream of dtype VFM_F32 or VFM_BF16 (h, delta, h_out, y all of that dtype; w fp32 [D]):
+ *   delta != NULL: h_out = round(h + delta) (written when h_out != NULL) and the norm reads that rounded sum;
+ *   y != NULL: y = round(w * (x * rsqrt(mean(x^2) + eps))), fp32 arithmetic, one rounding;
+ *   y == NULL: the residual add alone (delta and h_out required).
+ * D a multiple of 4, at most 2048 (else VFM_NO_KERNEL). */
+int vfm_rms_norm_rows(const void* h, const void* delta, void* h_out, const float* w, void* y, int dtype, int rows,
+                      int D, float eps, void* stream);
+
+/* SwiGLU rows: gu [rows, 2 Ip] (gate columns 0..Ip, up columns Ip..2 Ip) -> out [rows, Ip],
+ * out = round(round(silu(gate)) * up) for columns < I, exactly zero for columns I..Ip. Ip a multiple of 4. */
+int vfm_swiglu_rows(const void* gu, void* out, int dtype, int rows, int I, int Ip, void* stream);
+
+/* Patch gather: img fp32 [B, 3, H, W] (normalised), idx int32 [rows] = raster patch id (b gh + py) gw + px of
+ * each output row -> out [rows, Kp] (dtype_out), out[t, c P^2 + i P + j] = img[b, c, P py + i, P px + j],
+ * columns K = 3 P^2 .. Kp zero. Rows whose id is out of range are written as zeros. */
+int vfm_patch_gather(const float* img, const int* idx, void* out, int dtype_out, int B, int H, int W, int P,
+                     int rows, int K, int Kp, void* stream);
+
 /* 3x3 / stride 1 / pad 1 convolution, NHWC fp32, implicit GEMM on bf16 MFMA with fp32-equivalent
  * products (precision VFM_F32: the 6-term split; VFM_F32X3: the opt-in 3-term one). Replaces the
  * MIOpen fp32 convolutions of the LPIPS VGG16 stack, reference training/lpips.py:126-163, forward

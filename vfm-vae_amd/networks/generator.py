@@ -562,7 +562,8 @@ class Generator(nn.Module):
         self.vfm_encoder = VFMEncoder(model_name=vfm_name, conditional=conditional, label_type=label_type,
                                       scale_factor=scale_factor, patch_from_layers=patch_from_layers)
         ps = self.vfm_encoder.patch_size
-        self.patch_resolutions = [int(img_resolution * scale_factor // ps) for _ in patch_from_layers]
+        strides = self.vfm_encoder.token_strides or [ps] * len(patch_from_layers)
+        self.patch_resolutions = [int(img_resolution * scale_factor // s) for s in strides]
         assert img_resolution * scale_factor % ps == 0, \
             f'Image resolution {img_resolution * scale_factor} must be divisible by the VFM patch size {ps}.'
         self.z_resolution = int(img_resolution // resolution_compression_factor)

@@ -38,14 +38,25 @@ class VFMEncoder(nn.Module):
             from .vfms.clip_utils import CLIPVisionEncoder
             self.encoder = CLIPVisionEncoder(model_name=model_name, patch_from_layers=patch_from_layers,
                                              scale_factor=scale_factor, amp_dtype=amp_dtype, amp_enabled=amp_enabled)
+        elif "qwen" in name:
+            from .vfms.qwen_utils import QwenVisionEncoder
+            self.encoder = QwenVisionEncoder(model_name=model_name, conditional=conditional, label_type=label_type,
+                                             scale_factor=scale_factor, patch_from_layers=patch_from_layers,
+                                             amp_dtype=amp_dtype, amp_enabled=amp_enabled)
         else:
             raise NotImplementedError(
                 f"VFM backbone '{model_name}' is not part of the MI355X training path "
-                "(supported: siglip2, dinov2, clip)")
+                "(supported: siglip2, dinov2, clip, qwen)")
 
     @property
     def patch_size(self) -> int:
         return self.encoder.patch_size
+
+    @property
+    def token_strides(self):
+        """Pixels per token of each `patch_from_layers` entry, for backbones whose outputs do not all live on
+        the patch grid (Qwen2.5-VL: the merged -1 output); None: every entry is on the patch_size grid."""
+        return getattr(self.encoder, "token_strides", None)
 
     # ------------------------------------------------------------------ feature reuse
     # The frozen tower runs once per phase on the same microbatch (reference loss.py: the D

@@ -57,6 +57,10 @@ SIGNATURES = {
     "vfm_codebook_argmax": [c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp, c_vp],
     "vfm_residual_layer_norm": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp],
     "vfm_layer_norm_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp],
+    "vfm_rope_attention_varlen": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_int, c_vp],
+    "vfm_rms_norm_rows": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp],
+    "vfm_swiglu_rows": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
+    "vfm_patch_gather": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "vfm_layer_norm_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp],
     "vfm_pw_gemm_gelu": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                          c_vp],

@@ -330,6 +330,8 @@ _ROC = {
     "attention_fwd": "attn_fwd_d64",
     "ssim_fwd": "ssim_fwd", "ssim_bwd": "ssim_bwd",
     "gram_topk": "gram_topk_kernel", "cknna_terms": "cknna_rows",
+    "rms_norm_rows": "rms_rows<{T}, ",
+    "swiglu_rows": "swiglu_rows<{T}>", "patch_gather": "patch_gather<{T}>",
 }
 _NP = {"f32x6": 3, "f32x3": 2, "bf16": 1}
 _TNAME = {"f32": "float", "bf16": "__hip_bfloat16", "f16": "__half", "f64": "double"}
@@ -379,6 +381,8 @@ def rocprof_name(region):
             return f"attn32_fwd<{np_}, {occ}>"
         occ = 2 if (np_ == 3 and os.environ.get("VFM_ATTN32_DKDV_OCC", "2") != "1") else 1
         return f"attn32_dkdv<{np_}, {occ}>"
+    if base == "rope_attention_varlen" and len(args) == 3:     # rope_attn_varlen_d80<waves per workgroup>
+        return f"rope_attn_varlen_d{args[1]}<{args[2]}>"
     if base == "convnext_mlp_fwd" and len(args) == 3:          # mlp_fwd<C, SAVE>
         return f"mlp_fwd<{args[1]}, {args[2]}>"
     pat = _ROC.get(base)

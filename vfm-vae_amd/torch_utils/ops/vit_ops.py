@@ -200,3 +200,111 @@ def sdpa(q, k, v):
             # [B, h, N, N] score tensor)
             q = q.contiguous()
     return F.scaled_dot_product_attention(q, k, v)
+
+
+# ------------------------------------------------------------------------------------------------
+# Qwen2.5-VL vision tower (networks/utils/vfms/qwen_utils.py): RMSNorm on a stream of the compute dtype,
+# SwiGLU over the padded gate | up projection, the patch gather into window order and the varlen RoPE
+# attention. ROCm tensors outside autograd run csrc/qwen.hip (qwen_hip); the torch formulations below
+# are the CPU path and what a kernel that does not take a shape (VFM_NO_KERNEL cases: fp32 attention,
+# other head dims) falls back to. VFM_QWEN_OPS=torch: the torch formulations on ROCm tensors too (A/B, with
+# VFM_VIT_GEMM=torch for the GEMMs: tools_dev/qwenbench.py).
+QWEN_OWN = os.environ.get("VFM_QWEN_OPS", "hip") == "hip"
+
+
+def rms_norm(h, weight, eps):
+    """weight * rmsnorm(h) in h's dtype: fp32 statistics and product, one rounding (HF Qwen2_5_VLRMSNorm)."""
+    return residual_rms_norm(h, None, weight, eps)[1]
+
+
+def residual_rms_norm(h, delta, weight, eps):
+    """(h + delta, weight * rmsnorm(h + delta)), both in h's dtype; the norm reads the rounded sum. delta None:
+    (h, rmsnorm(h)); weight None: (h + delta, None)."""
+    if QWEN_OWN and _frozen(h, delta, weight):
+        from . import qwen_hip
+        if qwen_hip.rows_supported(h) and (delta is None or delta.dtype == h.dtype):
+            return qwen_hip.rms_norm(h, delta, weight, eps, want_y=weight is not None)
+    if delta is not None:
+        h = h + delta.to(h.dtype)
+    if weight is None:
+        return h, None
+    x = h.float()
+    y = weight.float() * (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps))
+    return h, y.to(h.dtype)
+
+
+def swiglu(gu, inter):
+    """gu [..., 2 Ip] (gate | up, each zero-padded from `inter` to Ip columns) -> silu(gate) * up [..., Ip];
+    silu is rounded to gu's dtype before the product, columns inter..Ip are zeros."""
+    if QWEN_OWN and _frozen(gu):
+        from . import qwen_hip
+        if gu.dtype in (torch.float32, torch.bfloat16) and gu.shape[-1] % 8 == 0:
+            return qwen_hip.swiglu(gu, inter)
+    Ip = gu.shape[-1] // 2
+    out = F.silu(gu[..., :Ip]) * gu[..., Ip:]
+    if inter < Ip:
+        out[..., inter:] = 0
+    return out
+
+
+def patch_rows(img, idx, patch, Kp, dtype):
+    """Normalised image fp32 [B, 3, H, W] -> [T, Kp] rows of `dtype`: row t is patch idx[t] (raster id
+    (b gh + py) gw + px) flattened (c, i, j), zero-padded from 3 patch^2 to Kp columns."""
+    if QWEN_OWN and _frozen(img) and img.dtype == torch.float32:
+        from . import qwen_hip
+        return qwen_hip.patch_gather(img, idx, patch, Kp, dtype)
+    B, C, H, W = img.shape
+    gh, gw = H // patch, W // patch
+    x = img.reshape(B, C, gh, patch, gw, patch).permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gw, C * patch * patch)
+    x = x.index_select(0, idx.long()).to(dtype)
+    return F.pad(x, (0, Kp - x.shape[1]))
+
+
+def rotate_half(x):
+    d = x.shape[-1] // 2
+    return torch.cat((-x[..., d:], x[..., :d]), -1)
+
+
+def rope_attention_varlen(qkv, cos, sin, seg, heads):
+    """Block-diagonal self-attention with rotary position embedding over packed tokens.
+    qkv [T, 3 * heads * d] (q | k | v); cos / sin fp32 [T, d]; seg: `Segments` (cu_seqlens on the device for
+    the kernel, the same lengths on the host for this torch formulation) -> [T, heads * d].
+    q and k are rotated in fp32 and rounded back to qkv's dtype before QK^T (HF apply_rotary_pos_emb_vision)."""
+    T, D3 = qkv.shape
+    d = D3 // (3 * heads)
+    if QWEN_OWN and _frozen(qkv):
+        from . import qwen_hip
+        if qwen_hip.attention_supported(qkv, d):
+            return qwen_hip.rope_attention_varlen(qkv, cos, sin, seg.cu, heads, seg.max_len)
+    q, k, v = qkv.reshape(T, 3, heads, d).unbind(1)
+    c, s = cos[:, None, :].float(), sin[:, None, :].float()
+    q = (q.float() * c + rotate_half(q.float()) * s).to(qkv.dtype)
+    k = (k.float() * c + rotate_half(k.float()) * s).to(qkv.dtype)
+    out = torch.empty(T, heads, d, dtype=qkv.dtype, device=qkv.device)
+    for start, length, count in seg.runs:        # `count` consecutive segments of one length: one batched call
+        sl = slice(start, start + length * count)
+        qs, ks, vs = (t[sl].reshape(count, length, heads, d).transpose(1, 2) for t in (q, k, v))
+        out[sl] = F.scaled_dot_product_attention(qs, ks, vs).transpose(1, 2).reshape(length * count, heads, d)
+    return out.reshape(T, heads * d)
+
+
+class Segments:
+    """Segment list of a varlen attention: `cu` int32 [S + 1] on the device (built once, never read back),
+    `lengths` on the host, `max_len`, and `runs` = (start, length, count) of consecutive equal lengths."""
+
+    def __init__(self, lengths, device):
+        self.lengths = [int(x) for x in lengths if int(x) > 0]
+        cu = [0]
+        for n in self.lengths:
+            cu.append(cu[-1] + n)
+        self.cu = torch.tensor(cu, dtype=torch.int32).to(device)
+        self.max_len = max(self.lengths)
+        self.total = cu[-1]
+        self.runs = []
+        pos = 0
+        for n in self.lengths:
+            if self.runs and self.runs[-1][1] == n:
+                self.runs[-1][2] += 1
+            else:
+                self.runs.append([pos, n, 1])
+            pos += n
