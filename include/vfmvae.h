@@ -18,7 +18,8 @@
  *   - Return value: VFM_OK (0) on success, VFM_ERR_ARGS (-2) for an invalid
  *     argument, VFM_NO_KERNEL (-1) when no specialisation exists
  *     (`vfm_filtered_lrelu`, mirroring `filtered_lrelu.cpp:51-56`, the window
- *     length of `vfm_ssim_*`, k > 64 of `vfm_gram_topk` / `vfm_cknna_terms`), or a
+ *     length of `vfm_ssim_*`, k > 64 of `vfm_gram_topk` / `vfm_cknna_terms`, k + 1 > 64 of
+ *     `vfm_knn_radius`, an input dtype `vfm_feature_stats_accum` has no kernel for), or a
  *     positive hipError_t from the launch.
  *   - dtype codes: VFM_F32, VFM_F16, VFM_BF16, VFM_F64. Arithmetic is fp32
  *     (fp64 for VFM_F64); filters are always fp32.
@@ -807,6 +808,37 @@ int vfm_gram_topk(const float* feats, long long ld, int N, int D, int k, int exc
 long long vfm_cknna_terms_ws(int N);
 int vfm_cknna_terms(const int* idxK, const float* valK, const int* idxL, const float* valL, int N, int k, double* out,
                     void* ws, void* stream);
+
+/* ---- Evaluation metrics: Frechet-distance statistics and improved precision / recall ------------------
+ * vfm_feature_stats_accum (replaces metrics/metric_utils.py:109-124 `FeatureStats.append`: the batch copied to
+ *   the host, `x64.sum(axis=0)` and `x64.T @ x64` in numpy): x [n][ld] (VFM_F32 or VFM_F16, ld >= D), in place
+ *   raw_mean[D] += sum_r x_r and raw_cov[D][D] += X^T X, both fp64 and device resident. Inputs are widened to
+ *   fp64 before the product (exact products, fp64 accumulation on the f64 MFMA); the full square is written.
+ *   Every element has one owner and one summation order: no atomics, independent of the grid. n >= 0, D >= 1
+ *   (else VFM_ERR_ARGS); other dtypes VFM_NO_KERNEL.
+ * vfm_knn_radius (replaces metrics/precision_recall.py:53-56: cdist blocks of the manifold against itself,
+ *   copied to the host, `dist.float().kthvalue(nhood_size + 1).values.half()`): feats fp16 [N][ld] -> radii
+ *   fp16 [nrows], the (k + 1)-th smallest Euclidean distance of row row0 + i to all N rows, itself included
+ *   (a row slice per rank; row0 = 0, nrows = N for all rows). Squared
+ *   distances are max((|a|^2 + |b|^2) - 2 a.b, 0) in fp32, a.b on the fp16 MFMA with one fp32 accumulator over
+ *   the whole of D; sqrtf correctly rounded, fp16 by round-to-nearest-even. No distance matrix in memory; the
+ *   result does not depend on `splits`. k >= 0, k + 1 <= N, D >= 1 (else VFM_ERR_ARGS); k + 1 <= 64 (else
+ *   VFM_NO_KERNEL). ws holds vfm_knn_radius_ws bytes.
+ * vfm_manifold_hits (replaces metrics/precision_recall.py:58-62: cdist blocks of the probes against the
+ *   manifold on the host, `(dist <= kth).any(dim=1)` and the mean): probes fp16 [P][ldp], manifold fp16
+ *   [N][ldm], radii fp16 [N] -> hits[P] bytes, 1 iff some j has sqrtf(d2(i, j)) <= float(radii[j]) (the
+ *   distance arithmetic of vfm_knn_radius), and *mean (device) = count / P in fp32. ws holds
+ *   vfm_manifold_hits_ws bytes.
+ * The _ws queries return the workspace bytes (negative: VFM_ERR_ARGS) and store the column split count used
+ *   for `splits` (0: chosen to fill the chip; at most 64) in *chosen. */
+int vfm_feature_stats_accum(const void* x, int dtype, long long ld, int n, int D, double* raw_mean, double* raw_cov,
+                            void* stream);
+long long vfm_knn_radius_ws(int N, int k, int nrows, int splits, int* chosen);
+int vfm_knn_radius(const void* feats, long long ld, int N, int D, int k, int row0, int nrows, int splits, void* radii,
+                   void* ws, void* stream);
+long long vfm_manifold_hits_ws(int P, int N, int splits, int* chosen);
+int vfm_manifold_hits(const void* probes, long long ldp, int P, const void* manifold, long long ldm, int N, int D,
+                      const void* radii, int splits, unsigned char* hits, float* mean, void* ws, void* stream);
 
 /* ---- BatchNormLocal (1-d) + LeakyReLU of the projected discriminator's heads (replaces
  * networks/discriminator.py:45-71 + the head blocks' nn.LeakyReLU(0.2), :102-109): x fp32 [B, C, L] in

@@ -9,12 +9,17 @@ two folders' file names, images mapped to [-1, 1], and the same reductions:
   * PSNR: per image `10·log10(2² / mse)` (torchmetrics `PeakSignalNoiseRatio(data_range=2)`
     called one image at a time, as the reference does), averaged.
 torchmetrics is not installed here, so SSIM/PSNR parity rests on the restatement (unpinned).
+
+Beyond the reference's CLI: `--metrics fid pr [--detector-dir DIR] [--nhood-size 3]` adds the Frechet distance
+and improved precision / recall between the two folders through the metrics package
+(`evaluate_distribution_metrics`); without the flag nothing changes.
 """
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import common  # noqa: E402
@@ -71,6 +76,59 @@ def evaluate_image_metrics(ref_dir, pred_dir, batch_size=64, num_workers=8, devi
     return res
 
 
+@torch.no_grad()
+def evaluate_distribution_metrics(ref_dir, pred_dir, metrics=("fid", "pr"), detector_dir=None, nhood_size=3,
+                                  batch_size=64, num_workers=8, device=None, log=print):
+    """FID and improved precision / recall between the images of --ref-dir (the real set) and of --pred-dir (the
+    reconstructions), through the metrics package: detector features of both folders into FeatureStats (on the
+    fidstats kernel on a GPU), frechet_distance, and knn_radius / manifold_hits. The detectors (Inception-v3 for
+    fid, VGG16 for pr) are files in --detector-dir (else VFM_DETECTOR_DIR, else the dnnlib cache)."""
+    from metrics import frechet_inception_distance as fid_mod, metric_utils, precision_recall
+    unknown = sorted(set(metrics) - {"fid", "pr"})
+    if unknown:
+        raise ValueError(f"unknown metrics {unknown}; choose from fid, pr")
+    if detector_dir is not None:
+        os.environ["VFM_DETECTOR_DIR"] = str(detector_dir)
+    device = torch.device(device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
+    names = sorted(set(os.listdir(ref_dir)) & set(os.listdir(pred_dir)))
+    if not names:
+        raise ValueError(f"No overlapping files found between {ref_dir} and {pred_dir}")
+    pool = common.Writer(workers=max(1, num_workers)).pool
+    batches = [names[i:i + batch_size] for i in range(0, len(names), batch_size)]
+    res = {"total": len(names)}
+    for metric in metrics:
+        url = fid_mod.INCEPTION_URL if metric == "fid" else precision_recall.VGG16_URL
+        detector = metric_utils.get_feature_detector(url, device=device)
+        kw = dict(capture_mean_cov=True) if metric == "fid" else dict(capture_all=True)
+        stats = {}
+        for side, folder in (("ref", ref_dir), ("pred", pred_dir)):
+            stats[side] = metric_utils.FeatureStats(**kw)
+            load = lambda batch, folder=folder: [common.load_png_uint8(os.path.join(folder, n)) for n in batch]
+            fut = pool.submit(load, batches[0])
+            for bi in range(len(batches)):
+                arrays = fut.result()
+                if bi + 1 < len(batches):
+                    fut = pool.submit(load, batches[bi + 1])
+                images = torch.from_numpy(np.stack(arrays)).to(device).permute(0, 3, 1, 2).contiguous()   # uint8 RGB
+                stats[side].append_torch(detector(images, return_features=True))
+        if metric == "fid":
+            mu_r, sigma_r = stats["ref"].get_mean_cov()
+            mu_p, sigma_p = stats["pred"].get_mean_cov()
+            res["fid"] = fid_mod.frechet_distance(mu_p, sigma_p, mu_r, sigma_r)
+        else:
+            real = stats["ref"].get_all_torch().to(torch.float16).to(device)
+            gen = stats["pred"].get_all_torch().to(torch.float16).to(device)
+            res["precision"] = precision_recall.manifold_fraction(real, gen, nhood_size)
+            res["recall"] = precision_recall.manifold_fraction(gen, real, nhood_size)
+    pool.shutdown(wait=True)
+    if "fid" in res:
+        log(f"FID          : {res['fid']:.4f}")
+    if "precision" in res:
+        log(f"Precision    : {res['precision']:.4f}")
+        log(f"Recall       : {res['recall']:.4f}")
+    return res
+
+
 if __name__ == "__main__":
     import argparse
     p = argparse.ArgumentParser(description="Evaluate LPIPS / PSNR / SSIM between image pairs.")
@@ -78,5 +136,12 @@ if __name__ == "__main__":
     p.add_argument("--pred-dir", type=str, required=True, help="Path to predicted images.")
     p.add_argument("--batch-size", type=int, default=64, help="Batch size for GPU inference.")
     p.add_argument("--num-workers", type=int, default=8, help="Number of loader threads.")
+    p.add_argument("--metrics", nargs="+", choices=["fid", "pr"], default=None,
+                   help="Also compute FID and / or precision / recall between the two folders.")
+    p.add_argument("--detector-dir", type=str, default=None, help="Folder with the detector files (fid, pr).")
+    p.add_argument("--nhood-size", type=int, default=3, help="Neighbourhood size of precision / recall.")
     a = p.parse_args()
     evaluate_image_metrics(a.ref_dir, a.pred_dir, batch_size=a.batch_size, num_workers=a.num_workers)
+    if a.metrics:
+        evaluate_distribution_metrics(a.ref_dir, a.pred_dir, metrics=a.metrics, detector_dir=a.detector_dir,
+                                      nhood_size=a.nhood_size, batch_size=a.batch_size, num_workers=a.num_workers)

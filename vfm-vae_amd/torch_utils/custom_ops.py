@@ -132,6 +132,11 @@ SIGNATURES = {
     "vfm_gram_topk": [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
     "vfm_cknna_terms_ws": [c_int],
     "vfm_cknna_terms": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
+    "vfm_feature_stats_accum": [c_vp, c_int, c_ll, c_int, c_int, c_vp, c_vp, c_vp],
+    "vfm_knn_radius_ws": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "vfm_knn_radius": [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp],
+    "vfm_manifold_hits_ws": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "vfm_manifold_hits": [c_vp, c_ll, c_int, c_vp, c_ll, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp],
     "vfm_dwconv2d_bwd_weight_mfma_tiles": [c_int, c_int, c_int, c_int, c_int, c_int],
     "vfm_dwconv2d_bwd_weight_mfma": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "vfm_bnl1d_lrelu_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_vp],
@@ -294,6 +299,8 @@ def get_native():
             lib.vfm_dwconv2d_fwd_mfma_units.restype = c_ll
             lib.vfm_gram_topk_ws.restype = c_ll
             lib.vfm_cknna_terms_ws.restype = c_ll
+            lib.vfm_knn_radius_ws.restype = c_ll
+            lib.vfm_manifold_hits_ws.restype = c_ll
             _lib = lib
     return _lib
 

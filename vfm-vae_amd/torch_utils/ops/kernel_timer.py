@@ -330,6 +330,7 @@ _ROC = {
     "attention_fwd": "attn_fwd_d64",
     "ssim_fwd": "ssim_fwd", "ssim_bwd": "ssim_bwd",
     "gram_topk": "gram_topk_kernel", "cknna_terms": "cknna_rows",
+    "feature_stats_accum": "xtx_kernel<{T}>", "knn_radius": "dist_kernel<0>", "manifold_hits": "dist_kernel<1>",
     "rms_norm_rows": "rms_rows<{T}, ",
     "swiglu_rows": "swiglu_rows<{T}>", "patch_gather": "patch_gather<{T}>",
 }

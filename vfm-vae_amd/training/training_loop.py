@@ -652,6 +652,35 @@ def construct_iteration(G, D, G_ema, device, loss_kwargs, G_opt_kwargs, D_opt_kw
                              bucket_mb=bucket_mb)
 
 
+def check_metric_detectors(metrics):
+    """Every detector file the metrics need must resolve on the local disk (metrics/metric_utils.py
+    get_feature_detector never opens a URL)."""
+    if not metrics:
+        return
+    from metrics import metric_main, metric_utils
+    for metric in metrics:
+        for url in metric_main.detector_urls(metric):
+            path = metric_utils.detector_path(url)
+            if not os.path.isfile(path):
+                raise NotImplementedError(f"metrics {metrics}: the FID/IS detectors need URL downloads (reference "
+                                          "metrics/), which this offline build does not fetch; set `metrics: []` "
+                                          f"or put the detector file at {path}")
+
+
+def evaluate_metrics(metrics, G_ema, training_set_kwargs, device, run_dir, snapshot_path, stats_metrics):
+    """calc_metric / report_metric for every configured metric (reference training_loop.py:409-422, :805-813)."""
+    if not metrics:
+        return
+    from metrics import metric_main
+    dist.print0('Evaluating metrics...')
+    for metric in metrics:
+        result = metric_main.calc_metric(metric=metric, G=G_ema, dataset_kwargs=training_set_kwargs,
+                                         num_gpus=dist.get_world_size(), rank=dist.get_rank(), device=device)
+        if dist.get_rank() == 0:
+            metric_main.report_metric(result, run_dir=run_dir, snapshot_path=snapshot_path)
+        stats_metrics.update(result.results)
+
+
 def save_snapshot(path, G, D, G_ema, training_set_kwargs):
     torch.save({"G": G.state_dict(), "D": D.state_dict(), "G_ema": G_ema.state_dict(),
                 "training_set_kwargs": dict(training_set_kwargs)}, path)
@@ -674,9 +703,8 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     torch.manual_seed(base_seed)
     random.seed(base_seed)
     configure_backends(cudnn_benchmark)
-    if metrics:
-        raise NotImplementedError(f"metrics {metrics}: the FID/IS detectors need URL downloads (reference "
-                                  "metrics/), which this offline build does not fetch; set `metrics: []`")
+    metrics = list(metrics or [])
+    check_metric_detectors(metrics)                    # a missing detector fails the run here, not at a snapshot
 
     dist.print0('Loading training set...')
     training_set = dnnlib.util.construct_class_by_name(**training_set_kwargs)
@@ -703,6 +731,7 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
     loss = step.loss
 
     stats_collector = training_stats.Collector(regex='.*')
+    stats_metrics = dict()
     stats_jsonl = open(os.path.join(run_dir, 'stats.jsonl'), 'at') if dist.get_rank() == 0 else None
     cur_nimg = resume_kimg * 1000
     cur_tick = 0
@@ -721,9 +750,10 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
             exhausted = True
         if one_epoch and _sync_all_done(exhausted, device):      # reference _sync_all_done :349-353
             dist.print0(f'[one-epoch] data exhausted at {cur_nimg / 1e3:.1f} kimg')
+            snapshot_pth = os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:08d}.pth')
             if dist.get_rank() == 0 and network_snapshot_ticks is not None:
-                save_snapshot(os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:08d}.pth'), G, D, G_ema,
-                              training_set_kwargs)
+                save_snapshot(snapshot_pth, G, D, G_ema, training_set_kwargs)
+            evaluate_metrics(metrics, G_ema, training_set_kwargs, device, run_dir, snapshot_pth, stats_metrics)
             break
         step(phase_real_img, phase_real_c, cur_nimg)
         cur_nimg += batch_size
@@ -747,12 +777,14 @@ def training_loop(run_dir='.', training_set_kwargs={}, validation_set_kwargs={},
         dist.print0(f"tick {cur_tick:<5d} kimg {cur_nimg / 1e3:<8.1f} sec/kimg {sec_per_kimg:<7.2f} "
                     f"img/s {1e3 / max(sec_per_kimg, 1e-9):<8.1f} maintenance {maintenance_time:<6.1f}")
         if (network_snapshot_ticks is not None) and (done or cur_tick % network_snapshot_ticks == 0) and cur_tick > 0:
+            snapshot_pth = os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:08d}.pth')
             if dist.get_rank() == 0:
-                save_snapshot(os.path.join(run_dir, f'network-snapshot-{cur_nimg // 1000:08d}.pth'), G, D, G_ema,
-                              training_set_kwargs)
+                save_snapshot(snapshot_pth, G, D, G_ema, training_set_kwargs)
+            evaluate_metrics(metrics, G_ema, training_set_kwargs, device, run_dir, snapshot_pth, stats_metrics)
         stats_collector.update()
         if stats_jsonl is not None:
-            stats_jsonl.write(json.dumps(dict(stats_collector.as_dict(), timestamp=time.time())) + '\n')
+            metric_stats = {f'Metrics/{k}': v for k, v in stats_metrics.items()}
+            stats_jsonl.write(json.dumps(dict(stats_collector.as_dict(), **metric_stats, timestamp=time.time())) + '\n')
             stats_jsonl.flush()
         cur_tick += 1
         tick_start_nimg = cur_nimg
