@@ -441,6 +441,42 @@ int vfm_attention_f32_bwd(const void* q, const void* k, const void* v, const voi
                           const long long* sdv, float scale, int precision, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Attention over a short key list under a key-padding mask (csrc/xattn.hip): all keys of one (batch, head)
+ * are staged in LDS once, plain two-pass softmax. Masked keys get probability exactly 0. Every sample must keep
+ * at least one valid key (a query with none is outside the contract: NaN).
+ *
+ * vfm_attention_keymask_fwd: the SigLIP2 text tower's self-attention (HF SiglipTextModel with attention_mask
+ * under bf16 autocast, reference networks/utils/vfms/siglip2_utils.py encode_text). q, k, v, o bf16
+ * [B, N, H, head_dim] views with the stride convention of vfm_attention_fwd; key_mask uint8 [B, N] (non-zero =
+ * attend) or NULL (no mask). fp32 softmax statistics, P rounded to bf16 for P.V. Forward only. head_dim 64 and
+ * N <= 128, else VFM_NO_KERNEL. */
+int vfm_attention_keymask_fwd(const void* q, const void* k, const void* v, const void* key_mask, void* o, int B,
+                              int H, int N, int head_dim, const long long* sq, const long long* sk,
+                              const long long* sv, const long long* so, float scale, void* stream);
+/* vfm_cross_attention_f32_*: the decoder's text cross-attention with its learned null key / value (reference
+ * networks/utils/gigagan_utils.py:94-146), fp32 with gradients on the fp32-equivalent products of
+ * vfm_attention_f32_* (same precision codes). q [B, Nq, H, d] fp32 view (strides sq as vfm_attention_f32_fwd);
+ * kv [B, L, 2, H, d] contiguous (the to_kv linear's [B, L, 2 H d] output: all of k before all of v);
+ * null_kv [2, H, d]; key_mask uint8 [B, L] or NULL. Key 0 of every (b, h) is the null key / value, keys 1..L the
+ * text tokens. mask_null = 0: the null key is never masked; mask_null = 1: it is masked whenever key_mask is
+ * given (what the reference module computes: it prepends a False column to its boolean mask).
+ * d in {32, 64} and L + 1 <= 128, else VFM_NO_KERNEL; pointers 16-B aligned, strides multiples of 4.
+ *   fwd: o (strides so) and lse [B, H, Nq] (log2 domain);
+ *   bwd: dq (strides sdq), dkv in kv's layout (rows of masked keys: exact zeros), dnull [2, H, d] (summed over
+ *        the batch). No atomics: dK / dV partials of query chunks go through `workspace`
+ *        (vfm_cross_attention_f32_workspace_floats floats, 16-B aligned; negative return: an error code) and
+ *        are combined in index order, so two runs agree bit for bit. */
+long long vfm_cross_attention_f32_workspace_floats(int B, int H, int Nq, int L, int head_dim);
+int vfm_cross_attention_f32_fwd(const void* q, const void* kv, const void* null_kv, const void* key_mask, void* o,
+                                void* lse, int B, int H, int Nq, int L, int head_dim, const long long* sq,
+                                const long long* so, float scale, int mask_null, int precision, void* stream);
+int vfm_cross_attention_f32_bwd(const void* q, const void* kv, const void* null_kv, const void* key_mask,
+                                const void* o, const void* dout, const void* lse, void* workspace, void* dq,
+                                void* dkv, void* dnull, int B, int H, int Nq, int L, int head_dim,
+                                const long long* sq, const long long* so, const long long* sdo,
+                                const long long* sdq, float scale, int mask_null, int precision, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Dense GEMM on the MFMA cores with a fused epilogue (replaces the hipBLASLt GEMMs behind
  * torch.addmm / torch.bmm for the frozen ViT projections, reference
  * networks/utils/vfms/siglip2_utils.py:121 (HF SiglipEncoderLayer q/k/v/o, fc1 + gelu_tanh,

@@ -41,6 +41,18 @@ def c4(c):   # discrete latent (VQ, 8 codebooks of 4096 x 4), fp16 decoder block
     c["loss_kwargs"].update(compression_mode="discrete", kl_loss_weight=0.0, vq_loss_weight=1.0)
 
 
+def ctext(c):   # text conditioning: SigLIP2 text tower, pooled embedding into mapping / D heads, cross-attention
+    c["run_dir"] = "runs/synthetic_stage0_text"
+    c["training_set_kwargs"]["conditional"] = True
+    c["G_kwargs"]["use_cross_attn"] = True
+
+
+variant("vfm_vae_f16d32_siglip2_stage_0_text_synthetic.yaml",
+        "Text-conditional stage 0 on synthetic data (reference configs/vfm_vae_details.yaml: conditional,\n"
+        "label_type cls2text, use_cross_attn): the label string goes through the frozen SigLIP2 text tower; the\n"
+        "pooled embedding feeds the mapping network and the discriminator heads, the 64 text tokens are\n"
+        "cross-attended by decoder blocks 0-2 under the tokenizer's padding mask (csrc/xattn.hip). Without a\n"
+        "local checkpoint directory the tower is random-initialised and fed by the byte stand-in tokenizer.", ctext)
 variant("vfm_vae_f16d32_clip_b16_stage_0_cpu.yaml",
         "BASELINE config 0: f16d32 stage 0 with a CLIP ViT-B/16 encoder (a build addition: the reference\n"
         "does not ship CLIP as an encoder), batch 1 at 256^2 -- the CPU plumbing case.", c0)

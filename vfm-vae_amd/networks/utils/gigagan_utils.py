@@ -118,6 +118,14 @@ class CrossAttention(nn.Module):
         h, d = self.heads, self.dim_head
         x = self.norm(fmap).reshape(B, C, H * W)
         ctx = self.norm_context(context)
+        if self.to_out.bias is None and not decoder_ops.force_ref():
+            # fp32 ROCm inputs: both projections, the masked attention over [null ; text keys] and the output
+            # projection as one Function on csrc/xattn.hip (torch_utils/ops/xattn_hip.py); VFM_XATTN=torch: below
+            from torch_utils.ops import xattn_hip
+            if xattn_hip.supported(x, ctx, h, d):
+                y = xattn_hip.cross_attention(x, self.to_q.weight.reshape(h * d, C), self.to_kv.weight, ctx,
+                                              self.null_kv, self.to_out.weight.reshape(C, h * d), mask, h)
+                return y.reshape(B, C, H, W)
         q = _pointwise(self.to_q, x).reshape(B, h, d, H * W).transpose(2, 3)
         if q.is_cuda:                                   # fused SDPA needs stride(-1) == 1 (see SelfAttention)
             q = q.contiguous()

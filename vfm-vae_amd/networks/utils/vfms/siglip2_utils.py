@@ -29,7 +29,8 @@ import torch.nn.functional as F
 from torch_utils import distributed as dist
 from torch_utils.ops import vit_ops
 
-__all__ = ["SigLIP2Encoder", "SiglipVisionModel", "siglip_config_from_name"]
+__all__ = ["SigLIP2Encoder", "SiglipVisionModel", "SiglipTextModel", "ByteTokenizer", "siglip_config_from_name",
+           "siglip_text_config_from_name"]
 
 _SIZES = {  # hidden, layers, heads, intermediate
     "base": (768, 12, 12, 3072),
@@ -120,12 +121,13 @@ class SiglipAttention(nn.Module):
             self._fused = (key, w, b)
         return self._fused[1], self._fused[2]
 
-    def forward(self, x):
-        """x: [B, N, D] in compute dtype -> [B, N, D] compute dtype."""
+    def forward(self, x, key_mask=None):
+        """x: [B, N, D] in compute dtype -> [B, N, D] compute dtype. key_mask: bool [B, N] (True = attend; the
+        text tower's padding mask) or None."""
         B, N, D = x.shape
         w, b = self.fused_qkv(x.dtype)
         qkv = vit_ops.linear(x, w, b)                                         # [B, N, 3D]
-        o = vit_ops.attention_packed(qkv, self.num_heads)                     # [B, N, D]
+        o = vit_ops.attention_packed(qkv, self.num_heads, key_mask)           # [B, N, D]
         return vit_ops.linear(o, vit_ops.frozen_weight(self.out_proj.weight, x.dtype), self.out_proj.bias)
 
 
@@ -149,18 +151,18 @@ class SiglipEncoderLayer(nn.Module):
         self.layer_norm2 = nn.LayerNorm(d, eps=eps)
         self.mlp = SiglipMLP(cfg)
 
-    def forward(self, h, compute_dtype=torch.bfloat16):
+    def forward(self, h, compute_dtype=torch.bfloat16, key_mask=None):
         """h: fp32 residual stream [B, N, D]."""
-        a = self.self_attn(vit_ops.layer_norm(h, self.layer_norm1, compute_dtype))
+        a = self.self_attn(vit_ops.layer_norm(h, self.layer_norm1, compute_dtype), key_mask)
         h = vit_ops.residual_add(h, a)
         m = self.mlp(vit_ops.layer_norm(h, self.layer_norm2, compute_dtype))
         return vit_ops.residual_add(h, m)
 
-    def forward_chained(self, h, y1, next_ln, next_dtype, compute_dtype=torch.bfloat16):
+    def forward_chained(self, h, y1, next_ln, next_dtype, compute_dtype=torch.bfloat16, key_mask=None):
         """Same math as forward() with the LayerNorms fused into the residual adds:
         y1 = layer_norm1(h) (computed by the caller), returns (h_out, next_ln(h_out))
         (next_ln None -> (h_out, None))."""
-        a = self.self_attn(y1)
+        a = self.self_attn(y1, key_mask)
         h, y2 = vit_ops.residual_layer_norm(h, a, self.layer_norm2, compute_dtype)
         m = self.mlp(y2)
         if next_ln is None:
@@ -300,6 +302,174 @@ class SiglipVisionModel(nn.Module):
         return saved, last, pooled
 
 
+# ------------------------------------------------------------------------------------------------
+# Text tower (reference siglip2_utils.py:70-79, 140-164: HF SiglipTextModel under the encoder's autocast with the
+# tokenizer's padding mask). Same layer modules as the vision tower; the attention takes the key mask.
+
+TEXT_LENGTH = 64       # SigLIP's text length: padding="max_length", max_length=64
+
+
+class _Config(dict):
+    """A config dict whose entries also read as attributes (`Generator` reads `.config.hidden_size`)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None      # copy / pickle probe for dunder attributes this way
+
+
+def siglip_text_config_from_name(model_name: str) -> dict:
+    """Text architecture from a local config.json (`text_config` of a full SigLIP config, or a text-only one),
+    else from the HF naming convention. Without a local directory there is no tokenizer file either, so the
+    random-initialised tower is sized for the byte stand-in tokenizer (vocabulary 258)."""
+    cfg_path = os.path.join(model_name, "config.json")
+    if os.path.isdir(model_name) and os.path.exists(cfg_path):
+        cfg = json.load(open(cfg_path))
+        cfg = cfg.get("text_config", cfg)
+        hidden = cfg.get("hidden_size", 768)
+        return _Config(hidden_size=hidden, num_hidden_layers=cfg.get("num_hidden_layers", 12),
+                       num_attention_heads=cfg.get("num_attention_heads", 12),
+                       intermediate_size=cfg.get("intermediate_size", 3072), vocab_size=cfg.get("vocab_size", 32000),
+                       max_position_embeddings=cfg.get("max_position_embeddings", TEXT_LENGTH),
+                       layer_norm_eps=cfg.get("layer_norm_eps", 1e-6),
+                       projection_size=cfg.get("projection_size") or hidden)
+    name = os.path.basename(model_name.rstrip("/")).lower()
+    hidden, layers, heads, inter = _SIZES[next((k for k in _SIZES if k in name), "large")]
+    return _Config(hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=inter,
+                   vocab_size=ByteTokenizer.vocab_size, max_position_embeddings=TEXT_LENGTH, layer_norm_eps=1e-6,
+                   projection_size=hidden)
+
+
+class ByteTokenizer:
+    """Deterministic stand-in for the checkpoint's tokenizer when there is no local model directory (the
+    random-init path of the synthetic configs): ids = UTF-8 bytes + 2, then EOS = 1, right-padded with pad id 0
+    to max_length; attention_mask = 1 over bytes + EOS. Truncation cuts the id list (EOS included) at
+    max_length, so a text of max_length bytes or more keeps max_length byte ids and loses its EOS. Called like a
+    HF tokenizer; returns {"input_ids", "attention_mask"} int64 [B, max_length]."""
+    pad_token_id, eos_token_id, vocab_size = 0, 1, 258
+
+    def __call__(self, text, padding="max_length", max_length=TEXT_LENGTH, truncation=True, return_tensors="pt",
+                 return_attention_mask=True):
+        text = [text] if isinstance(text, str) else list(text)
+        ids = torch.full((len(text), max_length), self.pad_token_id, dtype=torch.int64)
+        mask = torch.zeros(len(text), max_length, dtype=torch.int64)
+        for i, t in enumerate(text):
+            seq = ([b + 2 for b in str(t).encode("utf-8")] + [self.eos_token_id])[:max_length]
+            ids[i, :len(seq)] = torch.tensor(seq, dtype=torch.int64)
+            mask[i, :len(seq)] = 1
+        return {"input_ids": ids, "attention_mask": mask}
+
+
+def load_tokenizer(model_name: str, pretrained: bool):
+    """(tokenizer, description): the checkpoint's own tokenizer from a local HF directory, else the byte stand-in.
+    The stand-in goes with a random-initialised tower only (no local directory, or one that holds a config.json
+    and no weights): a directory with text weights and no tokenizer files is an error, because ids from any other
+    tokenizer would be meaningless to those weights (and the pooled output is read at a pad position, so even
+    the pad id has to be the tokenizer's own)."""
+    names = ("tokenizer.json", "tokenizer.model", "spiece.model", "tokenizer_config.json")
+    has_files = os.path.isdir(model_name) and any(os.path.exists(os.path.join(model_name, n)) for n in names)
+    if not has_files and not pretrained:
+        return ByteTokenizer(), "byte stand-in tokenizer"
+    if not has_files:
+        raise FileNotFoundError(f"no tokenizer files ({', '.join(names)}) in {model_name}: text conditioning needs "
+                                "the tokenizer of the SigLIP2 checkpoint next to its weights")
+    from transformers import AutoTokenizer
+    return AutoTokenizer.from_pretrained(model_name), "checkpoint tokenizer"
+
+
+class SiglipTextEmbeddings(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        self.token_embedding = nn.Embedding(cfg["vocab_size"], cfg["hidden_size"])
+        self.position_embedding = nn.Embedding(cfg["max_position_embeddings"], cfg["hidden_size"])
+        self.register_buffer("position_ids", torch.arange(cfg["max_position_embeddings"]).expand((1, -1)),
+                             persistent=False)
+
+    def forward(self, input_ids):
+        n = input_ids.shape[-1]
+        if n > self.position_embedding.num_embeddings:
+            raise ValueError(f"sequence length {n} exceeds the {self.position_embedding.num_embeddings} positions")
+        return self.token_embedding(input_ids).float() + self.position_embedding.weight[:n].float()
+
+
+def _accept_text_prefix(state_dict, prefix, *args):
+    for k in list(state_dict.keys()):
+        if k.startswith(prefix + "text_model."):
+            state_dict[prefix + k[len(prefix) + len("text_model."):]] = state_dict.pop(k)
+
+
+class SiglipTextModel(nn.Module):
+    """HF `SiglipTextModel` (transformers 5 layout: embeddings, encoder.layers, final_layer_norm, head at the top
+    level; the `text_model.` prefix of transformers 4 and of the published checkpoints is accepted on load).
+    pooled = head(final_layer_norm(h)[:, -1]): the LAST position, which is a pad position for short texts."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.config = _Config(cfg)
+        self.embeddings = SiglipTextEmbeddings(cfg)
+        self.encoder = SiglipEncoder(cfg)
+        self.final_layer_norm = nn.LayerNorm(cfg["hidden_size"], eps=cfg["layer_norm_eps"])
+        self.head = nn.Linear(cfg["hidden_size"], cfg["projection_size"])
+        self._register_load_state_dict_pre_hook(_accept_text_prefix)
+
+    def reset_parameters(self, seed: int = 4321):
+        """Deterministic random init in the spirit of HF SiglipPreTrainedModel._init_weights."""
+        g = torch.Generator().manual_seed(seed)
+        d = self.config["hidden_size"]
+        with torch.no_grad():
+            for mod in self.modules():
+                if isinstance(mod, nn.Linear):
+                    bound = math.sqrt(6.0 / (mod.in_features + mod.out_features))
+                    mod.weight.copy_(torch.rand(mod.weight.shape, generator=g) * 2 * bound - bound)
+                    mod.bias.copy_(torch.randn(mod.bias.shape, generator=g) * 1e-6)
+                elif isinstance(mod, nn.LayerNorm):
+                    nn.init.ones_(mod.weight)
+                    nn.init.zeros_(mod.bias)
+                elif isinstance(mod, nn.Embedding):
+                    mod.weight.copy_(torch.randn(mod.weight.shape, generator=g) / math.sqrt(d))
+
+    def load_hf_checkpoint(self, path: str) -> bool:
+        """Load *.safetensors from a local HF directory: a full SigLIP checkpoint (`text_model.*`, next to the
+        vision tower's keys), a transformers 4 text-only one (same prefix) or a transformers 5 one (flat)."""
+        files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors")) if os.path.isdir(path) else []
+        if not files:
+            return False
+        from safetensors.torch import load_file
+        tops = ("embeddings", "encoder", "final_layer_norm", "head")
+        state, flat = {}, {}
+        for f in files:
+            for k, v in load_file(os.path.join(path, f)).items():
+                k = k[len("model."):] if k.startswith("model.text_model.") else k
+                if k.startswith("text_model."):
+                    state[k[len("text_model."):]] = v
+                elif k.split(".")[0] in tops:
+                    flat[k] = v
+        if not state:          # flat keys belong to the text tower only when no prefixed ones exist (a flat
+            state = flat       # vision-only checkpoint has embeddings.* / encoder.* / head.* of its own)
+        missing, _ = self.load_state_dict(state, strict=False)
+        missing = [k for k in missing if not k.endswith("position_ids")]
+        if missing:
+            raise RuntimeError(f"SigLIP checkpoint {path} is missing {len(missing)} text tensors, e.g. {missing[:3]}")
+        return True
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask=None, compute_dtype=torch.bfloat16):
+        """-> (last_hidden_state fp32 [B, N, D], pooler_output [B, projection] in the compute dtype)."""
+        key_mask = None if attention_mask is None else attention_mask.bool()
+        h = self.embeddings(input_ids)
+        layers = self.encoder.layers
+        y = vit_ops.layer_norm(h, layers[0].layer_norm1, compute_dtype)
+        for i, layer in enumerate(layers, start=1):
+            nxt, ndt = (layers[i].layer_norm1, compute_dtype) if i < len(layers) else (self.final_layer_norm,
+                                                                                      torch.float32)
+            h, y = layer.forward_chained(h, y, nxt, ndt, compute_dtype, key_mask=key_mask)
+        last = y
+        x = last[:, -1].to(compute_dtype)
+        pooled = vit_ops.linear(x, vit_ops.frozen_weight(self.head.weight, compute_dtype), self.head.bias)
+        return last, pooled
+
+
 class SigLIP2Encoder(nn.Module):
     """Wrapper with the reference interface: `encode_image(img, eq_scale_factor,
     is_eq_prior) -> (patch_features, pooled)` and `encode_text(text)`."""
@@ -327,16 +497,25 @@ class SigLIP2Encoder(nn.Module):
         self.vision_model.eval().requires_grad_(False)
         self.pretrained_loaded = loaded
 
+        text = ""
         if conditional and label_type in ["text", "cls2text"]:
-            raise NotImplementedError("SigLIP2 text conditioning needs the HF text tower and tokenizer, "
-                                      "which are not part of the MI355X training path")
-        self.tokenizer = None
-        self.text_model = None
-        self.use_text = False
+            tcfg = siglip_text_config_from_name(model_name)
+            self.text_model = SiglipTextModel(tcfg)
+            self.text_model.reset_parameters()
+            tloaded = self.text_model.load_hf_checkpoint(model_name)
+            self.tokenizer, which = load_tokenizer(model_name, tloaded)
+            self.text_model.eval().requires_grad_(False)
+            self.use_text = True
+            text = (f", text tower {'pretrained' if tloaded else 'random init'} ({tcfg['num_hidden_layers']} layers, "
+                    f"hidden {tcfg['hidden_size']}, vocabulary {tcfg['vocab_size']}) with the {which}")
+        else:
+            self.tokenizer = None
+            self.text_model = None
+            self.use_text = False
         n = cfg["num_hidden_layers"]
         dist.print0(f"SigLIP2Encoder ready: {model_name} ({'pretrained' if loaded else 'random init'}), "
                     f"{n} layers, hidden {cfg['hidden_size']}, patch {self.patch_size}, "
-                    f"layers {patch_from_layers}, scale_factor {scale_factor}")
+                    f"layers {patch_from_layers}, scale_factor {scale_factor}{text}")
 
     def _preprocess_image(self, img, eq_scale_factor, is_eq_prior):
         if img.dtype == torch.uint8:
@@ -373,4 +552,15 @@ class SigLIP2Encoder(nn.Module):
 
     @torch.no_grad()
     def encode_text(self, text):
-        return None, None, None
+        """-> (seq_tokens fp32 [B, 64, D], pooled fp32 [B, projection], mask bool [B, 64]), or three Nones for
+        an unconditional encoder. Reference siglip2_utils.py:140-164."""
+        if not self.use_text:
+            return None, None, None
+        # padding="max_length": that is how the model was trained
+        inputs = self.tokenizer(list(text), padding="max_length", max_length=TEXT_LENGTH, truncation=True,
+                                return_tensors="pt", return_attention_mask=True)
+        device = next(self.text_model.parameters()).device
+        ids, mask = inputs["input_ids"].to(device), inputs["attention_mask"].to(device)
+        dtype = self.amp_dtype if (self.amp_enabled and ids.is_cuda) else torch.float32
+        seq_tokens, pooled = self.text_model(ids, mask, compute_dtype=dtype)
+        return seq_tokens.float(), pooled.float(), mask.bool()

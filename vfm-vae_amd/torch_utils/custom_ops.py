@@ -208,6 +208,13 @@ SIGNATURES = {
     "vfm_event_elapsed": [c_vp, c_vp, c_fp],
     "vfm_attention_f32_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                               c_int, c_llp, c_llp, c_llp, c_llp, c_llp, c_llp, c_llp, c_llp, c_float, c_int, c_vp],
+    "vfm_attention_keymask_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_llp, c_llp, c_llp,
+                                  c_llp, c_float, c_vp],
+    "vfm_cross_attention_f32_workspace_floats": [c_int, c_int, c_int, c_int, c_int],
+    "vfm_cross_attention_f32_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_llp,
+                                    c_llp, c_float, c_int, c_int, c_vp],
+    "vfm_cross_attention_f32_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                    c_int, c_int, c_int, c_llp, c_llp, c_llp, c_llp, c_float, c_int, c_int, c_vp],
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
@@ -301,6 +308,7 @@ def get_native():
             lib.vfm_cknna_terms_ws.restype = c_ll
             lib.vfm_knn_radius_ws.restype = c_ll
             lib.vfm_manifold_hits_ws.restype = c_ll
+            lib.vfm_cross_attention_f32_workspace_floats.restype = c_ll
             _lib = lib
     return _lib
 

@@ -156,14 +156,25 @@ def residual_add(h, delta):
     return h + delta.float()
 
 
-def attention_packed(qkv, heads):
+def attention_packed(qkv, heads, key_mask=None):
     """Multi-head self-attention of a packed [B, N, 3*D] (q | k | v) projection -> [B, N, D].
     ROCm bf16 tensors outside autograd with head dim 64 (the frozen towers) run the fused
     HIP kernel (attn_hip, csrc/attention.hip) straight on the packed layout; everything
-    else (CPU, fp32 parity runs, other head dims) is torch SDPA."""
+    else (CPU, fp32 parity runs, other head dims) is torch SDPA.
+    key_mask: bool [B, N] (True = attend; the SigLIP2 text tower's padding mask) or None. With a mask the ROCm
+    bf16 path is xattn_hip's key-masked kernel (csrc/xattn.hip, N <= 128); VFM_XATTN=torch and everything else
+    is torch SDPA with the boolean mask."""
     B, N, D3 = qkv.shape
     D = D3 // 3
     d = D // heads
+    if key_mask is not None:
+        if _frozen(qkv):
+            from . import xattn_hip
+            if xattn_hip.OWN == "hip" and xattn_hip.keymask_supported(qkv, d, N):
+                return xattn_hip.keymask_attention_packed(qkv, heads, key_mask)
+        q, k, v = qkv.reshape(B, N, 3, heads, d).permute(2, 0, 3, 1, 4).unbind(0)
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=key_mask.bool()[:, None, None, :])
+        return o.transpose(1, 2).reshape(B, N, D)
     if _frozen(qkv):
         from . import attn_hip
         if attn_hip.supported(qkv, d):
