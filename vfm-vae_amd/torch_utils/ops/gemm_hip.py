@@ -39,6 +39,12 @@ def _layout(t, kdim_last):
     return None
 
 
+def _alloc(shape, dtype, dev):
+    """Uncached scratch of one product: the piece buffers of an fp32 operand and the split-K / batch-reduce
+    partials of gemm8 and the 128-tile kernel (tests/test_gemm_guard_gpu.py substitutes guarded buffers)."""
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
 FAST = True                 # large-tile LDS-DMA kernel (csrc/gemm8.hip) where it applies
 SPLIT8 = __import__("os").environ.get("VFM_GEMM8_SPLIT", "0") == "1"
 FAST_MIN_MN = 1 << 18       # below ~256k outputs the 128-tile kernel fills the chip better
@@ -58,10 +64,10 @@ def _split_f32(t3, R, K, kc, ld, sb, cache, stream):
         if hit is not None and hit[0] == key and not torch.cuda.is_current_stream_capturing():
             return hit[1]
     if kc:
-        dst = torch.empty((z, R, npc * K), dtype=torch.bfloat16, device=t3.device)
+        dst = _alloc((z, R, npc * K), torch.bfloat16, t3.device)
         res = (dst, True, npc * K, R * npc * K if sb else 0)
     else:
-        dst = torch.empty((z, npc * K, R), dtype=torch.bfloat16, device=t3.device)
+        dst = _alloc((z, npc * K, R), torch.bfloat16, t3.device)
         res = (dst, False, R, npc * K * R if sb else 0)
     rc = _lib.vfm_split_f32(t3.data_ptr(), dst.data_ptr(), R, K, ld, sb, res[3], z, prec, int(kc), stream)
     if rc == custom_ops.VFM_NO_KERNEL:
@@ -99,7 +105,7 @@ def _planar(t3, stream):
     hit = getattr(base, "_vfm_planar", None)
     if hit is not None and hit[0] == key and not capturing:
         return hit[1], off, n
-    dst = torch.empty((npc, n), dtype=torch.bfloat16, device=base.device)
+    dst = _alloc((npc, n), torch.bfloat16, base.device)
     rc = _lib.vfm_split_f32(base.data_ptr(), dst.data_ptr(), 1, n, n, 0, 0, 1, prec, 1, stream)
     if rc == custom_ops.VFM_NO_KERNEL:
         return None
@@ -449,7 +455,7 @@ def _try_gemm(A, B, out, bias, bias_dim, act, alpha, beta, out_dtype, splits, re
                 n = _lib.vfm_gemm8_workspace_floats(prec, M, N, K, z, kchunk, int(reduce_batch))
                 if n < 0:
                     raise custom_ops.NativeError("vfm_gemm8: split-K workspace too large")
-                ws = torch.empty(max(n, 1), dtype=torch.float32, device=A.device) if n > 0 else None
+                ws = _alloc(max(n, 1), torch.float32, A.device) if n > 0 else None
             # one timer region per kernel instantiation (rocprof: gemm8_kernel<AK, BK, OUTF32>)
             region = f"gemm8<{tag},{tb(fa_kc)},{tb(fb_kc)},{tb(out_dtype == torch.float32)}>"
             if kernel_timer.SHAPES:
@@ -468,7 +474,7 @@ def _try_gemm(A, B, out, bias, bias_dim, act, alpha, beta, out_dtype, splits, re
     ws = None
     if splits > 1 or reduce_batch:
         n = _lib.vfm_gemm_workspace_floats(M, N, z, splits, int(reduce_batch))
-        ws = torch.empty(n, dtype=torch.float32, device=A.device)
+        ws = _alloc(n, torch.float32, A.device)
     if A.dtype == torch.bfloat16:
         in_code, tag = custom_ops.VFM_BF16, "bf16"
     else:
