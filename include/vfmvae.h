@@ -145,7 +145,7 @@ int vfm_filtered_lrelu_act(void* x, unsigned char* s, int dtype,
 /* Channel RMS norm of the decoder attention blocks (replaces F.normalize(x, dim=1) * scale * gamma of
  * reference networks/utils/gigagan_utils.py:31-39 ChannelRMSNorm): fp32 contiguous [B, C, P];
  * rinv [B, P] = 1 / max(||x||, 1e-12) saved for the backward (may be null in the forward). The
- * backward writes dx, and dgamma [C] through the workspace gpart [vfm_channel_rms_norm_rows, C]
+ * backward writes dx, and dgamma [C] through the workspace gpart, channel-major [C, vfm_channel_rms_norm_rows]
  * (both null: no gamma gradient). */
 long long vfm_channel_rms_norm_rows(int B, int C, int P);
 int vfm_channel_rms_norm_fwd(const float* x, const float* gamma, float* y, float* rinv, int B, int C, int P,
