@@ -26,45 +26,26 @@
 //     the online-softmax rescale of O^T is lane-local (query on the lane);
 //   * exp2 domain: t = s * scale * log2(e); p = exp2(t - m); l summed from fp32 p, P rounded
 //     to bf16 for the PV product (as flash attention on the reference's GPUs).
-#include "vfm_common.h"
+#include "attn_frag.h"
 
 namespace {
 
 using namespace vfm;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace vfm::attn;
 
 constexpr int HD = 64;        // head dim
-constexpr int WAVES = 4;
 constexpr int QB = 32 * WAVES;  // query rows per workgroup
-constexpr int KT = 64;        // keys per tile
-constexpr int ROWB = HD * 2;  // bytes per K/V row in LDS
+constexpr int KT = TT;        // keys per tile
 
 struct AttnArgs {
     const __hip_bfloat16* q;
     const __hip_bfloat16* k;
     const __hip_bfloat16* v;
     __hip_bfloat16* o;
-    long long sqb, sqn, sqh, skb, skn, skh, svb, svn, svh, sob, son, soh;
+    Strides sq, sk, sv, so;
     int N, H;
     float c;  // scale * log2(e)
 };
-
-// byte offset of 16-B chunk `ch` (0..7) of key row `key` in a [64][64 x bf16] tile image
-__device__ __forceinline__ int kv_off(int key, int ch) { return key * ROWB + 16 * (ch ^ ((key >> 1) & 7)); }
-
-// (lo, hi) -> packed bf16 pair, RNE: one v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(vfm_f2{lo, hi}, vfm_bf16x2));
-}
-
-__device__ __forceinline__ float xchg32(float v) {
-    // value of lane l^32 (the other half of the wave)
-    return __int_as_float(__shfl_xor(__float_as_int(v), 32));
-}
 
 __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * KT * ROWB];  // K tile | V tile
@@ -77,15 +58,15 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
     const int N = a.N;
     const int q_row = blockIdx.x * QB + 32 * wave + r;
 
-    const __hip_bfloat16* qb = a.q + (long long)b * a.sqb + (long long)h * a.sqh;
-    const __hip_bfloat16* kb = a.k + (long long)b * a.skb + (long long)h * a.skh;
-    const __hip_bfloat16* vb = a.v + (long long)b * a.svb + (long long)h * a.svh;
+    const __hip_bfloat16* qb = a.q + (long long)b * a.sq.b + (long long)h * a.sq.h;
+    const __hip_bfloat16* kb = a.k + (long long)b * a.sk.b + (long long)h * a.sk.h;
+    const __hip_bfloat16* vb = a.v + (long long)b * a.sv.b + (long long)h * a.sv.h;
 
     // Q^T B-operand fragments: lane holds Q[q_row][16s + 8hh .. +7], s = 0..3
     bf16x8 qf[4];
     {
         const bool ok = q_row < N;
-        const __hip_bfloat16* qp = qb + (long long)(ok ? q_row : 0) * a.sqn + 8 * hh;
+        const __hip_bfloat16* qp = qb + (long long)(ok ? q_row : 0) * a.sq.n + 8 * hh;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             uint4 v4 = ok ? *reinterpret_cast<const uint4*>(qp + 16 * s) : make_uint4(0, 0, 0, 0);
@@ -101,8 +82,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
         for (int u = 0; u < 2; ++u) {
             const int key = t * KT + st_key0 + 32 * u;
             if (key < N) {
-                kreg[u] = *reinterpret_cast<const uint4*>(kb + (long long)key * a.skn + 8 * st_ch);
-                vreg[u] = *reinterpret_cast<const uint4*>(vb + (long long)key * a.svn + 8 * st_ch);
+                kreg[u] = *reinterpret_cast<const uint4*>(kb + (long long)key * a.sk.n + 8 * st_ch);
+                vreg[u] = *reinterpret_cast<const uint4*>(vb + (long long)key * a.sv.n + 8 * st_ch);
             } else {
                 kreg[u] = make_uint4(0, 0, 0, 0);
                 vreg[u] = make_uint4(0, 0, 0, 0);
@@ -118,9 +99,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
         }
     };
 
-    // transposed-read offsets of V for (key block kb, k-step s, element half e):
-    // lane 4q+p of its 16-lane group reads key  32kb + 16s + 8e + 4hh + q,  d = 32db + 16g1 + 4p
-    const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tp = lane & 3;
+    const TrLane tl{(lane >> 4) & 1, (lane >> 2) & 3, lane & 3, hh};   // transposed-read lane roles of V
 
     f32x16 oacc[2];
     oacc[0] = f32x16{};
@@ -143,7 +122,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + kv_off(32 * kbk + r, 2 * s + hh));
-                sacc[kbk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc[kbk], 0, 0, 0);
+                sacc[kbk] = mfma(kf, qf[s], sacc[kbk]);
             }
         }
         // ---- mask keys beyond N (last tile only)
@@ -152,10 +131,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
 #pragma unroll
             for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kbase + 32 * kbk + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                    if (key >= N) sacc[kbk][i] = -INFINITY;
-                }
+                for (int i = 0; i < 16; ++i)
+                    if (kbase + 32 * kbk + acc_row(i, hh) >= N) sacc[kbk][i] = -INFINITY;
         }
         // ---- online softmax (query = this lane's column; keys split over lane and lane^32)
         float mx = sacc[0][0];
@@ -196,16 +173,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
                 pv.w = pk[kbk][4 * s + 3];
                 const bf16x8 pf = __builtin_bit_cast(bf16x8, pv);
 #pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const int d = 32 * db + 16 * g1 + 4 * tp;
-                    const int key0 = 32 * kbk + 16 * s + 4 * hh + tq;
-                    const int o0 = kv_off(key0, d >> 3) + 8 * (tp & 1);
-                    const int o1 = kv_off(key0 + 8, d >> 3) + 8 * (tp & 1);
-                    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vs + o0));
-                    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vs + o1));
-                    const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[db], 0, 0, 0);
-                }
+                for (int db = 0; db < 2; ++db) oacc[db] = mfma(rd_tr1(vs, tl, kbk, s, db), pf, oacc[db]);
             }
         __syncthreads();
     }
@@ -214,16 +182,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64(AttnArgs a) {
     const float l = l_run + xchg32(l_run);
     if (q_row < N) {
         const float inv = 1.f / l;
-        __hip_bfloat16* op = a.o + (long long)b * a.sob + (long long)q_row * a.son + (long long)h * a.soh;
+        __hip_bfloat16* op = a.o + (long long)b * a.so.b + (long long)q_row * a.so.n + (long long)h * a.so.h;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                uint2 w;
-                w.x = pack_bf16(oacc[db][4 * gi + 0] * inv, oacc[db][4 * gi + 1] * inv);
-                w.y = pack_bf16(oacc[db][4 * gi + 2] * inv, oacc[db][4 * gi + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * db + 8 * gi + 4 * hh) = w;
-            }
+        for (int db = 0; db < 2; ++db) store_tr_bf16(op + 32 * db, oacc[db], hh, inv, HD - 32 * db);
     }
 }
 
@@ -236,20 +197,14 @@ extern "C" int vfm_attention_fwd(const void* q, const void* k, const void* v, vo
     if (!q || !k || !v || !o || !sq || !sk || !sv || !so) return VFM_ERR_ARGS;
     if (B <= 0 || H <= 0 || N <= 0 || B > 65535 || H > 65535) return VFM_ERR_ARGS;
     // 16-B vector loads of 8 bf16: every row start must be 16-B aligned (unit stride along d)
-    const long long* st[4] = {sq, sk, sv, so};
-    for (const long long* s : st)
-        for (int i = 0; i < 3; ++i)
-            if (s[i] % 8) return VFM_ERR_ARGS;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16) return VFM_ERR_ARGS;
+    if (!strides_ok(sq, 8) || !strides_ok(sk, 8) || !strides_ok(sv, 8) || !strides_ok(so, 8)) return VFM_ERR_ARGS;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o)) return VFM_ERR_ARGS;
     AttnArgs a;
     a.q = (const __hip_bfloat16*)q;
     a.k = (const __hip_bfloat16*)k;
     a.v = (const __hip_bfloat16*)v;
     a.o = (__hip_bfloat16*)o;
-    a.sqb = sq[0]; a.sqn = sq[1]; a.sqh = sq[2];
-    a.skb = sk[0]; a.skn = sk[1]; a.skh = sk[2];
-    a.svb = sv[0]; a.svn = sv[1]; a.svh = sv[2];
-    a.sob = so[0]; a.son = so[1]; a.soh = so[2];
+    a.sq = mk(sq); a.sk = mk(sk); a.sv = mk(sv); a.so = mk(so);
     a.N = N;
     a.H = H;
     a.c = scale * 1.4426950408889634f;

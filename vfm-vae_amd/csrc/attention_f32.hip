@@ -30,31 +30,19 @@
 //   attn32_dkdv  : keys on lanes; per 64-query tile recomputes S = Q K^T, P, dP = dO V^T,
 //                  dS, then dV^T += dO^T P and dK^T += Q^T dS (no atomics: dQ has its own pass).
 // K/V (or Q/dO) tiles are staged fp32 -> split -> LDS as NP bf16 images (128-B rows, 16-B chunks
-// XOR-swizzled by (row>>1)&7, as attention.hip), next tile prefetched into registers during the
+// XOR-swizzled by (row>>1)&7: kv_off of attn_frag.h), next tile prefetched into registers during the
 // current tile's math.
-#include "vfm_common.h"
+#include "attn_frag.h"
 
 #include <cstdlib>
 
 namespace {
 
 using namespace vfm;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace vfm::attn;
 
 constexpr int HD = 64;
-constexpr int WAVES = 4;
 constexpr int RB = 32 * WAVES;   // rows (queries or keys) owned by a workgroup
-constexpr int TT = 64;           // rows per streamed tile
-constexpr int ROWB = HD * 2;     // bytes per bf16 row image
-constexpr int IMG = TT * ROWB;   // bytes per tile image
-
-struct Strides {
-    long long b, n, h;
-};
 
 struct Args {
     const float *q, *k, *v, *o, *dout;
@@ -66,91 +54,8 @@ struct Args {
     float scale;
 };
 
-__device__ __forceinline__ int kv_off(int row, int ch) { return row * ROWB + 16 * (ch ^ ((row >> 1) & 7)); }
-
-// one operand fragment as its NP bf16 pieces
-template <int NP>
-struct Frag {
-    bf16x8 p[NP];
-};
-
-// 8 floats -> NP bf16x8 pieces
-template <int NP>
-__device__ __forceinline__ Frag<NP> split8(const float* x) {
-    uint32_t q[4][NP];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) split_pieces<NP>(x[2 * j], x[2 * j + 1], q[j]);
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) f.p[p] = __builtin_bit_cast(bf16x8, make_uint4(q[0][p], q[1][p], q[2][p], q[3][p]));
-    return f;
-}
-
-// B-operand fragments (k step s of a 32-row accumulator block): elements 8s .. 8s+7
-template <int NP, int S>
-__device__ __forceinline__ Frag<NP> split_acc(const f32x16& a) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = a[8 * S + j];
-    return split8<NP>(x);
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// c += a * b over the piece products (Terms<NP>, smallest first)
-template <int NP>
-__device__ __forceinline__ f32x16 mfmaN(const Frag<NP>& a, const Frag<NP>& b, f32x16 c) {
-#pragma unroll
-    for (int t = 0; t < Terms<NP>::N; ++t) c = mfma(a.p[Terms<NP>::a(t)], b.p[Terms<NP>::b(t)], c);
-    return c;
-}
-
-// the same with the smaller piece products into their own accumulator cs and hi.hi alone into c
-// (for the long reductions over keys / queries: full-magnitude roundings as in an fp32 GEMM of
-// exact products; cs is added once at the end)
-template <int NP>
-__device__ __forceinline__ void mfmaN2(const Frag<NP>& a, const Frag<NP>& b, f32x16& c, f32x16& cs) {
-#pragma unroll
-    for (int t = 0; t < Terms<NP>::N - 1; ++t) cs = mfma(a.p[Terms<NP>::a(t)], b.p[Terms<NP>::b(t)], cs);
-    c = mfma(a.p[0], b.p[0], c);
-}
-
-// A operand, rows of the tile images (piece p at img + p IMG): row `row`, k = d = 16s + 8hh .. +7
-template <int NP>
-__device__ __forceinline__ Frag<NP> rd_row(const unsigned char* img, int row, int s, int hh) {
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) f.p[p] = *reinterpret_cast<const bf16x8*>(img + p * IMG + kv_off(row, 2 * s + hh));
-    return f;
-}
-
-// A operand, transposed: rows = d of block db, k = tile rows of 32-row block blk, step s, in the
-// k order of an accumulator block used as B operand (split_acc<s>)
-struct TrLane {
-    int g1, tq, tp, hh;
-};
-template <int NP>
-__device__ __forceinline__ Frag<NP> rd_tr(const unsigned char* img, const TrLane& t, int blk, int s, int db) {
-    const int d = 32 * db + 16 * t.g1 + 4 * t.tp;
-    const int r0 = 32 * blk + 16 * s + 4 * t.hh + t.tq;
-    const int o0 = kv_off(r0, d >> 3) + 8 * (t.tp & 1);
-    const int o1 = kv_off(r0 + 8, d >> 3) + 8 * (t.tp & 1);
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + p * IMG + o0));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + p * IMG + o1));
-        f.p[p] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
-    return f;
-}
-
-// register staging of one 64 x 64 fp32 tile: thread t holds row t>>2, d = 16 (t&3) .. +15
-// (zeros for d >= hd)
-struct Stage {
-    float4 v[4];
-};
+// load one 64 x 64 fp32 tile into its register staging (Stage of attn_frag.h): rows row .. row + 63 of a
+// [nrows, hd] matrix
 __device__ __forceinline__ void stage_load(Stage& s, const float* base, long long sn, int row, int nrows, int hd,
                                            int tid) {
     const int r = tid >> 2, d0 = 16 * (tid & 3);
@@ -161,18 +66,6 @@ __device__ __forceinline__ void stage_load(Stage& s, const float* base, long lon
     } else {
 #pragma unroll
         for (int u = 0; u < 4; ++u) s.v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-template <int NP>
-__device__ __forceinline__ void stage_store(const Stage& s, unsigned char* img, int tid) {
-    const int r = tid >> 2, q = tid & 3;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const float x[8] = {s.v[2 * c].x, s.v[2 * c].y, s.v[2 * c].z, s.v[2 * c].w,
-                            s.v[2 * c + 1].x, s.v[2 * c + 1].y, s.v[2 * c + 1].z, s.v[2 * c + 1].w};
-        const Frag<NP> f = split8<NP>(x);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x8*>(img + p * IMG + kv_off(r, 2 * q + c)) = f.p[p];
     }
 }
 
@@ -198,19 +91,6 @@ __device__ __forceinline__ void load_fixed(const float* base, long long sn, int 
         f[s] = split8<NP>(x);
     }
 }
-
-// store a transposed accumulator pair (rows d, lane = row of the output): out[row][d] = f * acc, d < hd
-__device__ __forceinline__ void store_tr(float* p, const f32x16* acc, int hh, float f, int hd) {
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-        if (32 * db < hd)
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi)
-            *reinterpret_cast<float4*>(p + 32 * db + 8 * gi + 4 * hh) =
-                make_float4(acc[db][4 * gi] * f, acc[db][4 * gi + 1] * f, acc[db][4 * gi + 2] * f, acc[db][4 * gi + 3] * f);
-}
-
-__device__ __forceinline__ float xchg32(float v) { return __int_as_float(__shfl_xor(__float_as_int(v), 32)); }
 
 // ---------------------------------------------------------------------------------------------
 // OCC = 1: the next K/V tile prefetched into registers during the current tile's math (one wave per
@@ -268,7 +148,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn32_fwd(Args a) {
             for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
-                    if (kbase + 32 * kbk + (i & 3) + 8 * (i >> 2) + 4 * hh >= Nk) sacc[kbk][i] = -INFINITY;
+                    if (kbase + 32 * kbk + acc_row(i, hh) >= Nk) sacc[kbk][i] = -INFINITY;
         }
         float mx = sacc[0][0];
 #pragma unroll
@@ -389,6 +269,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn32_dq(Args a) {
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
+                // acc_row(i, hh) written out: through the helper attn32_dq<3, 1> allocates its registers differently
                 const int key = kbase + 32 * kbk + (i & 3) + 8 * (i >> 2) + 4 * hh;
                 const float p = key < Nk ? __builtin_amdgcn_exp2f(fmaf(s[i], c, -lse)) : 0.f;
                 s[i] = p * (dp[i] - dlt);
@@ -524,15 +405,6 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn32_dkdv(Args a) {
     }
 }
 
-bool strides_ok(const long long* s) {
-    if (!s) return false;
-    for (int i = 0; i < 3; ++i)
-        if (s[i] % 4) return false;   // 16-B float4 rows
-    return true;
-}
-Strides mk(const long long* s) { return Strides{s[0], s[1], s[2]}; }
-bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 int check_shape(int B, int H, int Nq, int Nk, int head_dim, int precision) {
     if (head_dim != HD && head_dim != 32) return VFM_NO_KERNEL;
     if (precision != VFM_F32 && precision != VFM_F32X3) return VFM_ERR_ARGS;
@@ -549,7 +421,7 @@ extern "C" int vfm_attention_f32_fwd(const void* q, const void* k, const void* v
     int rc = check_shape(B, H, Nq, Nk, head_dim, precision);
     if (rc != VFM_OK) return rc;
     if (!q || !k || !v || !o || !lse) return VFM_ERR_ARGS;
-    if (!strides_ok(sq) || !strides_ok(sk) || !strides_ok(sv) || !strides_ok(so)) return VFM_ERR_ARGS;
+    if (!strides_ok(sq, 4) || !strides_ok(sk, 4) || !strides_ok(sv, 4) || !strides_ok(so, 4)) return VFM_ERR_ARGS;
     if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o)) return VFM_ERR_ARGS;
     Args a{};
     a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v;
@@ -584,7 +456,7 @@ extern "C" int vfm_attention_f32_bwd(const void* q, const void* k, const void* v
     if (!q || !k || !v || !o || !dout || !lse || !delta || !dq || !dk || !dv) return VFM_ERR_ARGS;
     const long long* ss[8] = {sq, sk, sv, so, sdo, sdq, sdk, sdv};
     for (const long long* s : ss)
-        if (!strides_ok(s)) return VFM_ERR_ARGS;
+        if (!strides_ok(s, 4)) return VFM_ERR_ARGS;   // 16-B float4 rows
     const void* ps[8] = {q, k, v, o, dout, dq, dk, dv};
     for (const void* p : ps)
         if (!aligned16(p)) return VFM_ERR_ARGS;

@@ -8,8 +8,8 @@
 //   * the patch gather: normalised image -> patch rows in window order.
 //
 // ---- varlen RoPE attention -------------------------------------------------------------------------
-// The arithmetic is csrc/attention.hip's: swapped QK^T (S^T = K . Q^T, v_mfma_f32_32x32x16_bf16, one query
-// per lane), exp2-domain online softmax in fp32, P rounded to bf16 as the B operand of O^T = V^T . P^T.
+// The arithmetic is csrc/attention.hip's, on the helpers of csrc/attn_frag.h: swapped QK^T (S^T = K . Q^T,
+// v_mfma_f32_32x32x16_bf16, one query per lane), exp2-domain online softmax in fp32, P rounded to bf16 as the B operand of O^T = V^T . P^T.
 // Differences:
 //   * head dim 80 = 5 k-steps of 16 for QK^T; the PV product runs over 96 = 3 x 32 output rows, the V tile
 //     rows zero-padded from 80 to 96 in LDS (1/6 of the PV MFMAs multiply zeros);
@@ -36,16 +36,14 @@
 // result does not depend on other segments' (finite) K / V.
 #include <stdlib.h>
 
-#include "vfm_common.h"
+#include "attn_frag.h"
 
 namespace {
 
 using namespace vfm;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+// by name: the tile constants and the swizzled kv_off of attn_frag.h are for 128-B rows, not this file's
+using attn::bf16x8; using attn::s16x4; using attn::f32x16; using attn::lds_s16x4; using attn::mfma;
+using attn::acc_row; using attn::pack_bf16; using attn::xchg32; using attn::store_tr_bf16;
 
 constexpr int HD = 80;            // head dim
 constexpr int HALF = HD / 2;      // rotary pairing distance
@@ -63,13 +61,8 @@ struct VarlenArgs {
     float c;                      // scale * log2(e)
 };
 
+// byte offset of 16-B chunk `ch` (0..12) of key row `key`: unswizzled 208-B rows
 __device__ __forceinline__ int kv_off(int key, int ch) { return key * ROWB + 16 * ch; }
-
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(vfm_f2{lo, hi}, vfm_bf16x2));
-}
-
-__device__ __forceinline__ float xchg32(float v) { return __int_as_float(__shfl_xor(__float_as_int(v), 32)); }
 
 __device__ __forceinline__ void unpack8(const uint4& u, float* f) {
     f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
@@ -206,8 +199,9 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 1 : 2) void rope_attn_varlen_d80
         *reinterpret_cast<uint4*>(vs + kv_off(row, c + 5)) = st.vh;
     };
 
-    // transposed-read lane roles of V (csrc/attention.hip): lane 4q + p of its 16-lane group reads
-    // key 32 kb + 16 s + 8 e + 4 hh + q,  d = 32 db + 16 g1 + 4 p
+    // transposed-read lane roles of V (TrLane / rd_tr1 of attn_frag.h, written out here for the 208-B rows:
+    // through rd_tr1 with this layout the offset arithmetic compiles to other instructions): lane 4q + p of
+    // its 16-lane group reads key 32 kb + 16 s + 8 e + 4 hh + q,  d = 32 db + 16 g1 + 4 p
     const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tp = lane & 3;
 
     f32x16 oacc[3];
@@ -253,7 +247,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 1 : 2) void rope_attn_varlen_d80
 #pragma unroll
                 for (int s = 0; s < 5; ++s) {
                     const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + kv_off(32 * kbk + r, 2 * s + hh));
-                    sacc[kbk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc[kbk], 0, 0, 0);
+                    sacc[kbk] = mfma(kf, qf[s], sacc[kbk]);
                 }
             }
             // ---- keys outside this lane's segment
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 1 : 2) void rope_attn_varlen_d80
                 for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int key = kbase + 32 * kbk + (i & 3) + 8 * (i >> 2) + 4 * hh;
+                        const int key = kbase + 32 * kbk + acc_row(i, hh);
                         if (key < lo || key >= hi) sacc[kbk][i] = -INFINITY;
                     }
             }
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 1 : 2) void rope_attn_varlen_d80
                         const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vs + o1));
                         const bf16x8 vf =
                             __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-                        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[db], 0, 0, 0);
+                        oacc[db] = mfma(vf, pf, oacc[db]);
                     }
                 }
         }
@@ -329,15 +323,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 1 : 2) void rope_attn_varlen_d80
         const float inv = 1.f / l;
         __hip_bfloat16* op = a.o + (long long)q_row * H * HD + (long long)h * HD;
 #pragma unroll
-        for (int db = 0; db < 3; ++db)
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                if (32 * db + 8 * gi >= HD) continue;
-                uint2 w;
-                w.x = pack_bf16(oacc[db][4 * gi + 0] * inv, oacc[db][4 * gi + 1] * inv);
-                w.y = pack_bf16(oacc[db][4 * gi + 2] * inv, oacc[db][4 * gi + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * db + 8 * gi + 4 * hh) = w;
-            }
+        for (int db = 0; db < 3; ++db) store_tr_bf16(op + 32 * db, oacc[db], hh, inv, HD - 32 * db);   // cut at d = 80
     }
 }
 

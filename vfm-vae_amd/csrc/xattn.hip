@@ -32,31 +32,19 @@
 // alone, so two runs agree bit for bit. At the training shape (B = 32, H = 8) there are 256 (b, h)
 // pairs for 256 CUs and one chunk: the partial is the result.
 //
-// The fragment helpers below are the ones of attention_f32.hip / attention.hip (anonymous namespaces
-// there; kept apart so that no code generated for the existing kernels changes).
-#include "vfm_common.h"
+// Tile images, operand fragments and the transposed reads are those of attn_frag.h, shared with
+// attention_f32.hip / attention.hip; only the row-pointer loads and the key-validity bits are this file's.
+#include "attn_frag.h"
 
 namespace {
 
 using namespace vfm;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace vfm::attn;
 
 constexpr int HD = 64;
-constexpr int WAVES = 4;
 constexpr int RB = 32 * WAVES;   // rows (queries or keys) owned by a workgroup
-constexpr int TT = 64;           // rows per tile image
-constexpr int ROWB = HD * 2;     // bytes per bf16 row image
-constexpr int IMG = TT * ROWB;   // bytes per tile image
 constexpr int MAXK = 128;        // keys (null key included) a workgroup holds
 constexpr int CHUNK_TARGET = 256;   // workgroups the dK / dV pass aims for (a shape-only constant)
-
-struct Strides {
-    long long b, n, h;
-};
 
 struct XArgs {
     const float *q, *kv, *null_kv, *o, *dout;
@@ -71,8 +59,6 @@ struct XArgs {
     float scale;
 };
 
-__device__ __forceinline__ int kv_off(int row, int ch) { return row * ROWB + 16 * (ch ^ ((row >> 1) & 7)); }
-
 __device__ __forceinline__ bool key_valid(const unsigned char* mask, int mask_null, int L, int b, int j) {
     if (j > L) return false;
     if (!mask) return true;
@@ -86,83 +72,8 @@ __device__ __forceinline__ const float* key_row(const XArgs& a, int b, int h, in
                   : a.kv + ((((long long)b * a.L + (j - 1)) * 2 + which) * a.H + h) * a.hd;
 }
 
-template <int NP>
-struct Frag {
-    bf16x8 p[NP];
-};
-
-template <int NP>
-__device__ __forceinline__ Frag<NP> split8(const float* x) {
-    uint32_t q[4][NP];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) split_pieces<NP>(x[2 * j], x[2 * j + 1], q[j]);
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) f.p[p] = __builtin_bit_cast(bf16x8, make_uint4(q[0][p], q[1][p], q[2][p], q[3][p]));
-    return f;
-}
-
-template <int NP, int S>
-__device__ __forceinline__ Frag<NP> split_acc(const f32x16& a) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = a[8 * S + j];
-    return split8<NP>(x);
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <int NP>
-__device__ __forceinline__ f32x16 mfmaN(const Frag<NP>& a, const Frag<NP>& b, f32x16 c) {
-#pragma unroll
-    for (int t = 0; t < Terms<NP>::N; ++t) c = mfma(a.p[Terms<NP>::a(t)], b.p[Terms<NP>::b(t)], c);
-    return c;
-}
-// hi.hi into c, the smaller piece products into cs (added once at the end)
-template <int NP>
-__device__ __forceinline__ void mfmaN2(const Frag<NP>& a, const Frag<NP>& b, f32x16& c, f32x16& cs) {
-#pragma unroll
-    for (int t = 0; t < Terms<NP>::N - 1; ++t) cs = mfma(a.p[Terms<NP>::a(t)], b.p[Terms<NP>::b(t)], cs);
-    c = mfma(a.p[0], b.p[0], c);
-}
-
-// A operand, rows of a tile image (piece p at img + p IMG): row `row`, k = d = 16s + 8hh .. +7
-template <int NP>
-__device__ __forceinline__ Frag<NP> rd_row(const unsigned char* img, int row, int s, int hh) {
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) f.p[p] = *reinterpret_cast<const bf16x8*>(img + p * IMG + kv_off(row, 2 * s + hh));
-    return f;
-}
-
-// A operand, transposed: rows = d of block db, k = tile rows of 32-row block blk, step s, in the k order
-// of an accumulator block used as B operand (split_acc<s>)
-struct TrLane {
-    int g1, tq, tp, hh;
-};
-__device__ __forceinline__ bf16x8 rd_tr1(const unsigned char* img, const TrLane& t, int blk, int s, int db) {
-    const int d = 32 * db + 16 * t.g1 + 4 * t.tp;
-    const int r0 = 32 * blk + 16 * s + 4 * t.hh + t.tq;
-    const int o0 = kv_off(r0, d >> 3) + 8 * (t.tp & 1);
-    const int o1 = kv_off(r0 + 8, d >> 3) + 8 * (t.tp & 1);
-    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o0));
-    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o1));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-template <int NP>
-__device__ __forceinline__ Frag<NP> rd_tr(const unsigned char* img, const TrLane& t, int blk, int s, int db) {
-    Frag<NP> f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) f.p[p] = rd_tr1(img + p * IMG, t, blk, s, db);
-    return f;
-}
-
-// register staging of one 64 x 64 fp32 tile: thread t holds row t>>2, d = 16 (t&3) .. +15 (zeros for
-// d >= hd or a null row pointer)
-struct Stage {
-    float4 v[4];
-};
+// load this thread's part of one fp32 row into the register staging (Stage of attn_frag.h); zeros for
+// d >= hd or a null row pointer
 __device__ __forceinline__ void stage_row(Stage& s, const float* row, int hd, int tid) {
     const int d0 = 16 * (tid & 3);
     if (row && d0 < hd) {
@@ -174,19 +85,6 @@ __device__ __forceinline__ void stage_row(Stage& s, const float* row, int hd, in
         for (int u = 0; u < 4; ++u) s.v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
-template <int NP>
-__device__ __forceinline__ void stage_store(const Stage& s, unsigned char* img, int tid) {
-    const int r = tid >> 2, q = tid & 3;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const float x[8] = {s.v[2 * c].x, s.v[2 * c].y, s.v[2 * c].z, s.v[2 * c].w,
-                            s.v[2 * c + 1].x, s.v[2 * c + 1].y, s.v[2 * c + 1].z, s.v[2 * c + 1].w};
-        const Frag<NP> f = split8<NP>(x);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x8*>(img + p * IMG + kv_off(r, 2 * q + c)) = f.p[p];
-    }
-}
-
 // all keys of (b, h) -> LDS: tile t of K at lds + t NP IMG, of V at lds + (NT + t) NP IMG
 template <int NP, int NT>
 __device__ __forceinline__ void stage_keys(const XArgs& a, unsigned char* lds, int b, int h, int tid) {
@@ -224,27 +122,15 @@ __device__ __forceinline__ void load_fixed(const float* row, int hd, int hh, Fra
     for (int s = 0; s < 4; ++s) f[s] = split8<NP>(x[s]);
 }
 
-// store a transposed accumulator pair (rows d, lane = row of the output): out[d] = f * acc, d < hd
-__device__ __forceinline__ void store_tr(float* p, const f32x16* acc, int hh, float f, int hd) {
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-        if (32 * db < hd)
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi)
-            *reinterpret_cast<float4*>(p + 32 * db + 8 * gi + 4 * hh) =
-                make_float4(acc[db][4 * gi] * f, acc[db][4 * gi + 1] * f, acc[db][4 * gi + 2] * f, acc[db][4 * gi + 3] * f);
-}
-
-__device__ __forceinline__ float xchg32(float v) { return __int_as_float(__shfl_xor(__float_as_int(v), 32)); }
-
 // validity bits of the keys of tile t (bit = key - 64 t), the same in every wave
 __device__ __forceinline__ unsigned long long valid_bits(const unsigned char* mask, int mask_null, int L, int b, int t,
                                                          int lane) {
     return __ballot(key_valid(mask, mask_null, L, b, TT * t + lane));
 }
-// accumulator entry i of key block kbk holds key 32 kbk + (i & 3) + 8 (i >> 2) + 4 hh of its tile
+// accumulator entry i of key block kbk holds key 32 kbk + acc_row(i, hh) of its tile; vh = the tile's bits
+// already shifted down by 4 hh
 __device__ __forceinline__ bool bit_of(unsigned long long vh, int kbk, int i) {
-    return (vh >> (32 * kbk + (i & 3) + 8 * (i >> 2))) & 1ull;
+    return (vh >> (32 * kbk + acc_row(i, 0))) & 1ull;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -540,10 +426,6 @@ struct KmArgs {
     float c;
 };
 
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(vfm_f2{lo, hi}, vfm_bf16x2));
-}
-
 template <int NT>
 __global__ __launch_bounds__(64 * WAVES) void xattn_keymask_fwd(KmArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * NT * IMG];   // K tiles | V tiles
@@ -638,27 +520,11 @@ __global__ __launch_bounds__(64 * WAVES) void xattn_keymask_fwd(KmArgs a) {
         const float inv = 1.f / l;
         __hip_bfloat16* op = a.o + (long long)b * a.so.b + (long long)q_row * a.so.n + (long long)h * a.so.h;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                uint2 w;
-                w.x = pack_bf16(oacc[db][4 * gi + 0] * inv, oacc[db][4 * gi + 1] * inv);
-                w.y = pack_bf16(oacc[db][4 * gi + 2] * inv, oacc[db][4 * gi + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * db + 8 * gi + 4 * hh) = w;
-            }
+        for (int db = 0; db < 2; ++db) store_tr_bf16(op + 32 * db, oacc[db], hh, inv, HD - 32 * db);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-bool strides_ok(const long long* s, int mult) {
-    if (!s) return false;
-    for (int i = 0; i < 3; ++i)
-        if (s[i] % mult) return false;
-    return true;
-}
-Strides mk(const long long* s) { return Strides{s[0], s[1], s[2]}; }
-bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 // grid limits (B, H on grid y / z) and index arithmetic in int (Nq + tile, L + 1)
 bool dims_ok(int B, int H, int Nq, int L) {
     return B > 0 && H > 0 && Nq > 0 && L > 0 && B <= 65535 && H <= 65535 && Nq <= (1 << 30) && L <= (1 << 30);
